@@ -7,10 +7,19 @@ mimic_run_skb) launch.  Default workload = BASELINE.json configs[1]: 1 048 576 x
 packets, the ~36-slot parse+hash DROP/PASS classifier, per-CPU array map (E=4, S=8), one MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config classifier|pass8|parse5|flowtrack|skb]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (value, ms_per_step,
+the config).  --full adds everything else the line used to carry: the status / counter / hash-map
+readout, exact eBPF instruction counts (one more launch per batch), the roofline figures, the
+PCIe-inclusive host-resident rate and the CPU baselines.  --dump-outputs DIR writes the per-packet
+R0 and status of the last timed step as DIR/r0.npy (float64) and DIR/status.npy (float32); the
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 With N > 1 run under torch.distributed.run: every rank owns its own vCPUs and its own packet
 shard (weak scaling, no data-path collective); RCCL broadcasts the program bytes at setup and
-all-reduces the per-CPU verdict counters after the timed region (the sum-over-CPUs readout).
+with --full all-reduces the per-CPU verdict counters after the timed region (the sum-over-CPUs
+readout).
 
 roofline.traffic / valu_busy come from a committed rocprofv3 summary (profiles/*_pmc_*.json,
 written by tools/pmc_summary.py) whose kernel-source hash, workload and vCPU count match this
@@ -312,10 +321,21 @@ def host_resident_rate(vm, pid, wl, sched, chunks: int = 0, reps: int = 5):
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    # 100 timed steps: the barrier + synchronize around the region cost ~35 us once, 6 % of 20
-    # cfg-2 steps (26 us each) but 1 % of 100
-    ap.add_argument("--steps", type=int, default=100)
-    ap.add_argument("--warmup", type=int, default=3)
+    # 100 timed launches by default: the barrier + synchronize around the region cost ~35 us once, 6 %
+    # of 20 cfg-2 steps (26 us each) but 1 % of 100
+    ap.add_argument("--steps", type=int, default=0,
+                    help="timed steps: passes over one batch each (a config that runs several batches per "
+                         "launch takes ceil(steps / many) launches, the last one shorter; default: 100 launches)")
+    ap.add_argument("--warmup", type=int, default=-1,
+                    help="untimed steps before the timed ones (default: 3 launches)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check what the headline figure does not need: "
+                         "status / counter / hash-map readout, eBPF instruction counts, roofline figures, the "
+                         "host-resident (PCIe-inclusive) rate and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the last timed step's per-packet R0 (r0.npy, float64) and status (status.npy, "
+                         "float32) to DIR (a fixed seeded sample of the packets when the batch is larger than "
+                         f"{DUMP_MAX_PACKETS} packets; rank r > 0 of a multi-GPU run writes r0_rank<r>.npy)")
     ap.add_argument("--config", default="classifier", choices=sorted(CONFIGS))
     ap.add_argument("--packets", type=int, default=0, help="packets per GPU (default: the config's)")
     ap.add_argument("--vcpus", type=int, default=0, help="vCPUs per GPU (default: the config's, else packets/4)")
@@ -326,11 +346,12 @@ def parse_args(argv=None):
                          "256 MiB Infinity Cache)")
     ap.add_argument("--many", type=int, default=0,
                     help="batches per launch (mimic_run_xdp_many, up to 8: one owned-spread launch runs K of the "
-                         "rotated batches back to back); --steps counts launches, ms_per_step stays per batch "
-                         "(0: the config's default, 5 for the classifier, else 1)")
+                         "rotated batches back to back); --steps counts batches, ms_per_step is per batch "
+                         "(0: the config's default, 8 for the classifier, else 1)")
     ap.add_argument("--digest", action="store_true",
                     help="add sha256 digests of every rank's per-packet R0 (batch 0, after the timed region) and "
-                         "of the merged hash map's (key, value) records to the line (tests/test_gpu_bench_dist.py)")
+                         "of the merged hash map's (key, value) records to the line (tests/test_gpu_bench_dist.py); "
+                         "implies --full")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-host-resident", action="store_true", help="skip the PCIe-inclusive rate")
@@ -348,13 +369,33 @@ def parse_args(argv=None):
     ap.add_argument("--launch-selftest", action="store_true",
                     help="CPU rehearsal of the --gpus N launcher: gloo ranks run the setup / readout "
                          "collectives with no engine and rank 0 prints the launch facts")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    args.full = args.full or args.digest
+    return args
 
 
 # Working set the timed region must exceed: MI355X_MICROARCH.md's 256 MiB Infinity Cache (MALL)
 # serves re-read lines and FETCH_SIZE counts those hits, so a batch re-launched from cache would
 # report a cache rate as an HBM rate.
 ROTATE_BYTES = 384 << 20
+
+# --dump-outputs writes at most this many packets' results (12 bytes each: 48 MiB)
+DUMP_MAX_PACKETS = 1 << 22
+
+
+def dump_outputs(path: str, res, n: int, rank: int) -> None:
+    """The last timed step's per-packet results as .npy files: R0 (u64 on the device) as float64,
+    status as float32.  A batch of more than DUMP_MAX_PACKETS packets is sampled at fixed seeded
+    indices (ascending), the same in every run."""
+    os.makedirs(path, exist_ok=True)
+    r0 = res.r0[:n].cpu().numpy().view(np.uint64)
+    st = res.status[:n].cpu().numpy()
+    if n > DUMP_MAX_PACKETS:
+        idx = np.sort(np.random.default_rng(20240229).choice(n, DUMP_MAX_PACKETS, replace=False))
+        r0, st = r0[idx], st[idx]
+    sfx = f"_rank{rank}" if rank else ""
+    np.save(os.path.join(path, f"r0{sfx}.npy"), r0.astype(np.float64))
+    np.save(os.path.join(path, f"status{sfx}.npy"), st.astype(np.float32))
 
 
 def launch_ranks(args, argv) -> int:
@@ -441,6 +482,47 @@ def make_batches(wl, args, n, rank, dev, sched):
     return out
 
 
+def jit_cache_dir() -> str:
+    """The on-disk JIT kernel cache: MIMIC_JIT_CACHE if set, else .jitcache in the source tree, else
+    (a tree this user cannot write, e.g. someone else's checkout) the user's cache directory; ""
+    (no disk cache: kernels are compiled in this process) when none of them can be written."""
+    cands = [os.environ["MIMIC_JIT_CACHE"]] if os.environ.get("MIMIC_JIT_CACHE") else [
+        os.path.join(ROOT, ".jitcache"),
+        os.path.join(os.environ.get("XDG_CACHE_HOME") or os.path.expanduser("~/.cache"), "mimic_amd", "jitcache")]
+    for d in cands:
+        try:
+            os.makedirs(d, exist_ok=True)
+        except OSError:
+            continue
+        if os.access(d, os.W_OK | os.X_OK):
+            return d
+    return ""
+
+
+def headline(args, cfg, wl, vm, batches, n, ws, vpg, K, steps, warmup, launches, elapsed) -> dict:
+    """The result line of a plain run: the rate over the timed steps and what was run."""
+    return {
+        "metric": "Mpkts/s (device-resident, one XDP program over 64-1500B batches)",
+        "value": round(n * ws * steps / elapsed / 1e6, 3),
+        "unit": "Mpkts/s",
+        "n_gpus": ws,
+        "steps": steps,   # batches (a step is one pass over one batch); launches below
+        "warmup": warmup,
+        "launches": launches,
+        "ms_per_step": round(elapsed / steps * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u64",
+        "data": "synthetic (seeded PCG64 packet mix, SURVEY.md 8(d))",
+        "config": {"workload": cfg["workload"], "packets_per_gpu": n, "vcpus_per_gpu": vpg,
+                   "schedule": args.sched, "parallelism": f"dp{ws}", "batches_rotated": len(batches),
+                   "working_set_bytes": sum(int(w.buf.nbytes) + 21 * n for w, _, _ in batches),
+                   "program_slots": sum(len(p.raw) // 8 for p in wl.progs), "engine": vm.LastExec(),
+                   "batches_per_launch": K},
+    }
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     args = parse_args(argv)
@@ -454,9 +536,8 @@ def main(argv=None):
     if args.launch_selftest:
         selftest_rank(args, ws, rank, local)
         return 0
-    # compiled JIT kernels persist here across runs
-    os.environ.setdefault("MIMIC_JIT_CACHE", os.path.join(ROOT, ".jitcache"))
-    os.makedirs(os.environ["MIMIC_JIT_CACHE"], exist_ok=True)
+    # compiled JIT kernels persist across runs where a directory can be written
+    os.environ["MIMIC_JIT_CACHE"] = jit_cache_dir()
 
     import torch
 
@@ -519,15 +600,12 @@ def main(argv=None):
         sys.stderr.write("bench.py: --many needs an xdp_md config without map resets and a batch count K divides\n")
         return 2
 
-    def launch_many(k):   # batches k*K .. k*K + K - 1 (mod nb) in one mimic_run_xdp_many call
-        sel = [batches[(k * K + q) % nb] for q in range(K)]
-        vm.RunXDPMany(pid, [b for _, b, _ in sel], [r for _, _, r in sel], stream=stream, sync=False)
-
-    def launch(k):
-        if K > 1:
-            launch_many(k)
+    def launch(pos, k=1):   # steps pos .. pos + k - 1: batches pos % nb, ... of the rotation, in one launch
+        if K > 1:   # one mimic_run_xdp_many call
+            sel = [batches[(pos + q) % nb] for q in range(k)]
+            vm.RunXDPMany(pid, [b for _, b, _ in sel], [r for _, _, r in sel], stream=stream, sync=False)
             return
-        w, batch, res = batches[k % nb]
+        w, batch, res = batches[pos % nb]
         for m in reset:   # a fresh map per step: every flow of the batch is inserted again
             m.Reset(stream)
         if wl.skb:
@@ -536,30 +614,50 @@ def main(argv=None):
         else:
             vm.RunXDPBatch(pid, batch, res, stream=stream, sync=False)
 
-    for k in range(args.warmup):
-        launch(k)
+    def run_steps(pos, count):   # `count` steps from rotation position pos, K per launch (the last: the rest)
+        launches = 0
+        while count > 0:
+            k = min(K, count)
+            launch(pos, k)
+            pos, count, launches = pos + k, count - k, launches + 1
+        return launches
+
+    # --steps / --warmup count steps (batches); their defaults are 100 / 3 launches
+    steps = args.steps if args.steps > 0 else 100 * K
+    warmup = args.warmup if args.warmup >= 0 else 3 * K
+    run_steps(0, warmup)
     torch.cuda.synchronize(dev)
     if use_dist:
         dist.barrier()
     # device time of the timed region: two HIP events on the stream the kernels run on, around the
-    # K back-to-back launches (an event pair per launch would itself sit between the kernels)
+    # back-to-back launches (an event pair per launch would itself sit between the kernels)
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     ev0.record(stream)
-    for k in range(args.steps):
-        launch(args.warmup + k)
+    launches = run_steps(warmup, steps)
     ev1.record(stream)
     torch.cuda.synchronize(dev)
     if use_dist:
         dist.barrier()
     t1 = time.perf_counter()
     elapsed = t1 - t0
-    region_ms = ev0.elapsed_time(ev1)
-    st = np.concatenate([res.status[:n].cpu().numpy() for _, _, res in batches])
-    timed = [((args.warmup + k) * K + q) % nb for k in range(args.steps) for q in range(K)]
     if use_dist:
         elapsed = D.allreduce_max_f64(elapsed, cdev)
+    if args.dump_outputs:   # what the last timed step computed: the results of its batch
+        dump_outputs(args.dump_outputs, batches[(warmup + steps - 1) % nb][2], n, rank)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline(args, cfg, wl, vm, batches, n, ws, vpg, K, steps, warmup, launches, elapsed)),
+                  file=json_out, flush=True)
+        if use_dist:
+            dist.destroy_process_group()
+        vm.close()
+        return 0
+
+    region_ms = ev0.elapsed_time(ev1)
+    st = np.concatenate([res.status[:n].cpu().numpy() for _, _, res in batches])
+    timed = [(warmup + k) % nb for k in range(steps)]
 
     # sum-over-CPUs readout of the per-CPU counters (RCCL all-reduce across ranks); shared hash
     # maps: one replica per GPU, (key, value) records merged
@@ -600,9 +698,7 @@ def main(argv=None):
         steps_timed = float(D.allreduce_sum_u64([int(steps_timed)], cdev)[0])
 
     if rank == 0:
-        total_pkts = n * ws * args.steps * K
-        value = total_pkts / elapsed / 1e6
-        avg_launch_s = region_ms / (args.steps * K) / 1e3   # per batch (a launch runs K), gaps included
+        avg_launch_s = region_ms / steps / 1e3   # per batch (a launch runs K), gaps included
         alg_of = {b: algorithmic_bytes(batches[b][0], vpg) for b in set(timed)}
         alg = sum(alg_of[b] for b in timed) / len(timed)
         achieved = alg / avg_launch_s
@@ -612,27 +708,11 @@ def main(argv=None):
         # a profiled launch ran K batches: its bytes and time per batch, like alg and avg_launch_s
         prof_ns = (prof.get("kernel_stats") or {}).get("avg_ns") / K if prof and (prof.get("kernel_stats") or {}).get("avg_ns") else None
         prof_bytes = prof["bytes_per_launch"] / K if prof and prof.get("bytes_per_launch") else None
-        out = {
-            "metric": "Mpkts/s (device-resident, one XDP program over 64-1500B batches)",
-            "value": round(value, 3),
-            "unit": "Mpkts/s",
-            "n_gpus": ws,
-            "steps": args.steps * K,   # batches (a step is one pass over one batch); launches below
-            "warmup": args.warmup,
-            "launches": args.steps,
-            "ms_per_step": round(elapsed / (args.steps * K) * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u64",
-            "data": "synthetic (seeded PCG64 packet mix, SURVEY.md 8(d))",
-            "config": {"workload": cfg["workload"], "packets_per_gpu": n, "vcpus_per_gpu": vpg,
-                       "schedule": args.sched, "parallelism": f"dp{ws}", "batches_rotated": nb,
-                       "working_set_bytes": sum(int(w.buf.nbytes) + 21 * n for w, _, _ in batches),
-                       "program_slots": sum(len(p.raw) // 8 for p in wl.progs), "engine": vm.LastExec(),
-                       "kernel_src_hash": src_hash, "batches_per_launch": K},
+        out = headline(args, cfg, wl, vm, batches, n, ws, vpg, K, steps, warmup, launches, elapsed)
+        out["config"]["kernel_src_hash"] = src_hash
+        out.update({
             "insns_per_s": round(steps_timed / elapsed, 1),
-            "mean_insns_per_packet": round(steps_timed / (n * ws * args.steps * K), 3),
+            "mean_insns_per_packet": round(steps_timed / (n * ws * steps), 3),
             "roofline": {"bound": "hbm", "achieved": round(achieved / 1e9, 3), "peak": HBM_PEAK / 1e9,
                          "unit": "GB/s", "frac": round(achieved / HBM_PEAK, 5),
                          "traffic": prof_bytes,
@@ -648,7 +728,7 @@ def main(argv=None):
             "status_ok_frac": float((st == 0).mean()),
             "counters_sum": counters,
             "hash_keys": hash_keys,
-        }
+        })
         if digests:
             out["digests"] = digests
         if use_dist:

@@ -30,8 +30,8 @@ def jit_kernels():
 
 def _bench2(cfg):
     cmd = [sys.executable, "-u", "bench.py", "--gpus", "2", "--dist-backend", "gloo", "--one-device", "--config", cfg,
-           "--steps", str(STEPS), "--warmup", str(WARMUP), "--batches", "1", "--no-host-resident", "--no-cpu-baseline",
-           "--digest"]
+           "--steps", str(STEPS), "--warmup", str(WARMUP), "--batches", "1", "--full", "--no-host-resident",
+           "--no-cpu-baseline", "--digest"]
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)

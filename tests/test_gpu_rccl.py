@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def _bench(cfg, rccl):
     cmd = [sys.executable, "bench.py", "--config", cfg, "--packets", "65536", "--vcpus", "4096", "--steps", "2",
-           "--warmup", "1", "--batches", "1", "--no-host-resident", "--no-cpu-baseline"] + (["--rccl"] if rccl else [])
+           "--warmup", "1", "--batches", "1", "--full", "--no-host-resident", "--no-cpu-baseline"] + (["--rccl"] if rccl else [])
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)

@@ -13,7 +13,11 @@ TAG=${TAG:-r02}
 EXTRA=${EXTRA:-}
 D=gpurun_out/prof_${TAG}
 mkdir -p $D
-B="python3 bench.py --config $CFG --steps 10 --warmup 2 --no-cpu-baseline --no-host-resident $EXTRA"
+# 10 timed launches after 2 warm-up launches (pmc_summary.py's --skip 2 --keep 10): bench.py counts
+# steps in batches, so a run of K batches per launch (--many K in EXTRA, else the config's default)
+# is given 10 K and 2 K steps
+PER_LAUNCH=$(python3 -c "import sys, bench; a = bench.parse_args(sys.argv[1:]); print(a.many or bench.CONFIGS[a.config].get('many', 1))" --config $CFG $EXTRA) || exit $?
+B="python3 bench.py --config $CFG --steps $((10 * PER_LAUNCH)) --warmup $((2 * PER_LAUNCH)) $EXTRA"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $D/kt_$NAME -o a -- $B > $D/kt_$NAME.log 2>&1 || exit $?
 timeout -s KILL 200 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $D/fetch_$NAME -o a -- $B > $D/fetch_$NAME.log 2>&1 || exit $?
 timeout -s KILL 200 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $D/write_$NAME -o a -- $B > $D/write_$NAME.log 2>&1 || exit $?

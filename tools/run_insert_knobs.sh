@@ -9,7 +9,7 @@ unset MIMIC_JIT_CACHE
 : > $D/lines.jsonl
 run() {   # name env...
   local n=$1; shift
-  env "$@" timeout -k 10 300 python -u bench.py --config ${CFG:-flowtrack_insert} --no-host-resident --no-cpu-baseline \
+  env "$@" timeout -k 10 300 python -u bench.py --config ${CFG:-flowtrack_insert} --full --no-host-resident --no-cpu-baseline \
       > $D/$n.json 2> $D/$n.err || { tail -20 $D/$n.err; exit 1; }
   python3 -c "import json,sys; d=json.load(open('$D/$n.json')); d['variant']='$n'; print(json.dumps(d))" >> $D/lines.jsonl
   python3 -c "import json; d=json.load(open('$D/$n.json')); print('$n', d['ms_per_step'], d['roofline']['avg_launch_ms'])"
