@@ -136,6 +136,8 @@ class Gen {
         inc_knob = !(ic && ic[0] == '0');
         const char *hf = getenv("MIMIC_JIT_HASH");   // 0: hash-map lookups always through the generic helper
         hash_fast = !(hf && hf[0] == '0');
+        const char *rd = getenv("MIMIC_JIT_RETDISPATCH");   // BPF-to-BPF returns through one block per program
+        ret_dispatch = rd ? rd[0] == '1' : !fast_paths;     // (default: in kernels without fast paths)
         const char *ti = getenv("MIMIC_JIT_TAIL");   // 0: tail calls always through the generic helper
         tail_inline = !(ti && ti[0] == '0');
         const char *ce = getenv("MIMIC_JIT_CENSUS");   // 1: per-packet slow-path call counts in place of steps
@@ -220,6 +222,13 @@ class Gen {
                                // pointer to a device copy (a copy + event per new batch between kernels)
     bool hash_fast = true;     // MIMIC_JIT_HASH=0: no inline hash-map lookups
     bool tail_inline = true;   // MIMIC_JIT_TAIL=0: no inline tail calls
+    // An EXIT that pops a frame goes to its program's one return block (R<p>_) instead of carrying the
+    // switch over the return sites itself.  On in kernels without fast paths (MIMIC_JIT_FAST=0, which
+    // call their slow paths out of line): there a program whose calls land on an EXIT (quirk Q12), with
+    // six return sites, came back from a call with its step counter and saved registers wrong although
+    // the source read correctly (structured fuzz seed 93); the tail-call dispatch block
+    // D_ exists for the same kind of control flow.  MIMIC_JIT_RETDISPATCH=1 / 0: everywhere / nowhere.
+    bool ret_dispatch = false;
     bool census = false;       // MIMIC_JIT_CENSUS=1: diagnostics (tools/cold_census.py)
     // MIMIC_JIT_MEMTIME=1 (measurement only, tools/memtime.py): s_memrealtime (100 MHz) when each
     // packet's process starts (err_pc) and when its results are stored (steps)
@@ -568,6 +577,7 @@ class Gen {
         E.line("  const uint32_t P = kp.static_next + kp.stack_size + 1;");
         if (ctx == CTX_SKB) E.line("  const uint32_t SK_ = P;   // the sk_buff entry (skb.h)");
         E.line("  uint32_t ga_ = 0;   // the address of the current memory access");
+        if (ret_dispatch && any_local) E.line("  uint32_t ret_ = 0;   // the slot a popped frame returns to (R<p>_)");
         for (auto &f : fwd_store) E.line("  uint32_t fwd%u_%u_ = 0;   // value of the stack store at P%u slot %u", f.first, f.second, f.first, f.second);
         for (auto &u : spec_use)
             E.line("  %s sp%u_%u_ = 0;   // packet load of P%u slot %u, issued early", u.second == 8 ? "uint64_t" : "uint32_t",
@@ -1638,6 +1648,16 @@ class Gen {
                     fall(p, e - 1);
             }
         }
+        if (ret_dispatch && any_local) {   // the program's one return block (epc_: the EXIT that came here)
+            E.line("  R%u_:", p.id);
+            E.line("    switch (ret_) {");
+            for (uint32_t a = 1; a < p.n; a++) {
+                const DInsn &c = p.ins[a - 1];
+                if (all_leaders || AUX_H(c.aux) == H_CALL_LOCAL) E.line("    case %u: goto P%u_%u;", a, p.id, a);
+            }
+            E.line("    default: TERM(MIMIC_ERR_ENGINE_HELPER, epc_);");
+            E.line("    }");
+        }
     }
 
     // the branch prefix of a slow path: "else " (or an if's condition) gets [[unlikely]], so the
@@ -1983,6 +2003,7 @@ class Gen {
         E.line("    ga_ = %s;", addr(base, off).c_str());
         if (!deferred && elided.count({cur_prog, i})) {   // the write happens in the lookup's cold path
             const auto f = fast_forms(base, n, val);
+            E.line("    // %u: key store deferred into the lookup's cold path (analyze_elide)", i);
             E.line("    if (!(%s)) %s{ %s%s }", (f.at(0).scond.empty() ? f.at(0).cond : f.at(0).scond).c_str(), hint_knob ? "[[unlikely]] " : "", base == 10 && !spec_use.empty() ? "spv_ = 0u; " : "",
                    cold("cold_store(kp, sp_, ga_, " + std::to_string(n) + "u, " + val + ")", i).c_str());
             return;
@@ -2070,6 +2091,12 @@ class Gen {
             E.line("      r9 = priv_load(kp, L.lane, (fq + 4) * 8, 8);");
             E.line("      r10 = r10 - kp.frame_size;");
             E.line("      if (%uu <= spc + 1) TERM(MIMIC_ERR_PC_OOB, %u);", p.n, i);
+            if (ret_dispatch) {
+                E.line("      ret_ = spc + 1; epc_ = %d; goto R%u_;", (int)i, p.id);
+                E.line("    }");
+                E.line("    TERM(MIMIC_OK, %d);", proc ? (int)i : -1);
+                break;
+            }
             E.line("      switch (spc + 1) {");
             for (uint32_t a = 1; a < p.n; a++) {
                 const DInsn &c = p.ins[a - 1];
@@ -2145,6 +2172,14 @@ class Gen {
                 }
                 E.line("      if (!(%s)) %s%s } }", hfast.c_str(), hint_knob ? "[[unlikely]] " : "", cold("cold_lookup(kp, sp_)", i).c_str());
             } else {
+                // R1 is not an LD_IMM64 of this block: the generic helper reads the key from the
+                // stack, so a key store that analyze_elide deferred (analyze_fwd pairs store and call
+                // whatever R1 holds) is made here first
+                auto f = fwd_call.find({p.id, i});
+                if (f != fwd_call.end() && elided.count({p.id, f->second})) {
+                    const DInsn &sx = p.ins[f->second];
+                    store(f->second, insn_dst(sx), insn_off(sx), AUX_SZ(sx.aux), "fwd" + std::to_string(p.id) + "_" + std::to_string(f->second) + "_", true);
+                }
                 E.line("    %s", cold("cold_lookup(kp, sp_)", i).c_str());
             }
             break;

@@ -79,7 +79,8 @@ def spread_spec(progs: Sequence[Tuple[bytes, Sequence]], maps: Sequence[dict], v
     """What the engine's spread_build() generates the spread kernel from, for programs (raw,
     relocations) loaded next to ``maps`` (created in this order: map id = index) on a VM with
     ``vcpus`` vCPUs: (pc, shapes, lds_rows) -- the (program, slot, map id) of every LD_IMM64 slot
-    naming a per-CPU array's object, those maps' (id, E * S, S), and the LDS table's rows
+    naming a per-CPU array's object (one whose row E * S is a multiple of 8 bytes: the engine leaves
+    the others to the one-lane kernel), those maps' (id, E * S, S), and the LDS table's rows
     (min(ppb, V) when that many rows of the largest such row fit 32 KiB, else 0).  own: the owned
     form's (spread_build_own: min(256, 32 KiB / row) rows, bit 31 set)."""
     by_name = {m["name"]: (i, m) for i, m in enumerate(maps)}
@@ -90,6 +91,8 @@ def spread_spec(progs: Sequence[Tuple[bytes, Sequence]], maps: Sequence[dict], v
             if name not in by_name or by_name[name][1]["type"] != 6:
                 continue
             mid, m = by_name[name]
+            if (m["max_entries"] * m["value_size"]) % 8:    # spread_build: rows of whole 8-byte words only
+                continue
             src, off = raw[8 * slot + 1] >> 4, int.from_bytes(raw[8 * slot + 2:8 * slot + 4], "little", signed=True)
             if src == 1 or (src == 2 and off == 0):
                 pc.append((pi, slot, mid))

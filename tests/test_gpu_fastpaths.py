@@ -603,9 +603,60 @@ def test_fused_counter_increments(gpu, variant):
     assert len(set(o["r0"].tolist())) > 100
 
 
+# ---------------------------------------------------------------------------------------------
+# the deferred key store (jit.cpp analyze_elide) in front of a lookup that is not inlined: R1's
+# LD_IMM64 sits in an earlier block, so the call goes to the generic helper, which reads the key
+# from the stack -- the store must have been made (found by the structured fuzz, seeds 45-51: the
+# generic lookup read the unwritten word and answered for key 0)
+# ---------------------------------------------------------------------------------------------
+def _elide_generic_scenario(mtype):
+    items = [
+        A.mov64_reg(6, 1),
+        A.ldx(4, 2, 6, 0),
+        A.ldx(4, 3, 6, 4),
+        A.alu64("sub", 3, 2, reg=True),
+        A.alu64("and", 3, 7),                  # key = packet length & 7: 0..3 hit, 4..7 miss
+        A.ld_map_fd(1, "m"),
+        A.ja("next"),
+        "next",
+        A.stx(4, 10, -4, 3),
+        A.mov64_reg(2, 10),
+        A.alu64("add", 2, -4),
+        A.call(A.FN_MAP_LOOKUP_ELEM),
+        A.jmp("jeq", 0, 0, "miss"),
+        A.ldx(8, 0, 0, 0),
+        A.exit_(),
+        "miss",
+        A.mov64_imm(0, 0xdead),
+        A.exit_(),
+    ]
+    init = [("m", k.to_bytes(4, "little"), (0x1000 * (k + 1) + c).to_bytes(8, "little"), c)
+            for k in range(4) for c in (range(4) if mtype in (5, 6) else [0])]
+    return Scenario(vcpus=4, progs=[_prog("elg", items)], map_init=init,
+                    maps=[dict(name="m", type=mtype, key_size=4, value_size=8, max_entries=4)])
+
+
+@pytest.mark.parametrize("mtype", [6, 2, 1, 5])
+def test_deferred_key_store_before_generic_lookup(gpu, mtype):
+    from mimic_amd import jit as J
+
+    sc = _elide_generic_scenario(mtype)
+    src = J.kernel_source(*kernel_of(sc))
+    assert "key store deferred into the lookup's cold path" in src and "lookup_fast" not in src.split("mimic_jit_kernel")[1]
+    pk = [bytes([i & 0xFF]) * (i % 23) for i in range(600)]
+    buf, off, lens = packets_to_buffer(pk)
+    cpu = W.schedule_cpu(len(pk), 4, "interleaved")
+    o = run_oracle(sc, buf, off, lens, cpu)
+    e = run_engine(sc, buf, off, lens, cpu)
+    assert_same(o, e)
+    assert e["last_exec"] == "jit"
+    assert len(set(o["r0"].tolist())) >= 5      # every key's value and the miss
+
+
 def jit_kernels():
     ks = [kernel_of(Scenario(vcpus=4, progs=[_stack_window_prog(v)])) for v in range(4)]
     ks += [kernel_of(_inc_scenario(v)) for v in range(4)]
+    ks += [kernel_of(_elide_generic_scenario(t)) for t in (6, 2, 1, 5)]
     ks += [kernel_of(sc) for sc in _escape_scenarios()]
     ks += [kernel_of(_hash_scenario(*c)) for c in HASH_CASES]
     ks += [kernel_of(_tail_scenario(b)) for b in (0, 3)]

@@ -200,7 +200,8 @@ def test_every_gpu_test_kernel_generates():
     from mimic_amd import jit as J
 
     count = 0
-    for name in ("test_gpu_kat", "test_gpu_skb", "test_gpu_parity", "test_gpu_hash", "test_gpu_fastpaths", "test_gpu_vc"):
+    for name in ("test_gpu_kat", "test_gpu_skb", "test_gpu_parity", "test_gpu_hash", "test_gpu_fastpaths", "test_gpu_vc",
+                 "test_gpu_fuzz_struct"):
         mod = importlib.import_module(name)
         for k in mod.jit_kernels():
             assert "mimic_jit_kernel" in J.kernel_source(*k)
