@@ -49,8 +49,7 @@ extern "C" int mimic_launch_skb_gather(const uint8_t *const *mem, uint32_t n, ui
                                        mimic_skb_custom *cust, const uint8_t *has_cust, hipStream_t st);
 extern "C" int mimic_launch_skb_prep(const uint8_t *pkt_data, const uint64_t *pkt_off, const uint32_t *pkt_len,
                                      uint32_t n, uint64_t *rec, uint32_t rec_q, uint64_t *prefix, uint64_t *state,
-                                     uint64_t init_base, uint32_t use_init, uint32_t rooms, uint32_t sparse,
-                                     uint32_t *rooms_state, hipStream_t st);
+                                     uint64_t init_base, uint32_t use_init, uint32_t *rooms_state, hipStream_t st);
 
 namespace {
 
@@ -221,7 +220,7 @@ struct mimic_vm {
     int spread_mode = -1;   // mimic_set_spread: -1 the default policy (env MIMIC_SPREAD), 0 never, 1 whenever allowed
     bool spread_lds = false;   // the spread kernel keeps a block's counters in LDS (else agent-scope atomics)
     int last_exec = 0;          // the kernel the last batch ran on
-    // launch parameters of JIT kernels in device memory: a ring of slots written by
+    // launch parameters of the batch interpreter in device memory: a ring of slots written by
     // stream-ordered copies from pinned host memory (a repeated batch reuses its slot)
     static constexpr int KP_SLOTS = 64;
     KParams *d_kp = nullptr, *h_kp = nullptr;
@@ -327,7 +326,7 @@ static int fail(mimic_vm *vm, int code, const char *fmt, ...) {
 
 static int skb_settle(mimic_vm *vm);
 
-// the device copy of kp for a JIT launch on stream st (see mimic_vm::d_kp)
+// the device copy of kp for a batch-interpreter launch on stream st (see mimic_vm::d_kp)
 static int kp_slot(mimic_vm *vm, const KParams &kp, hipStream_t st, const KParams **out) {
     if (!vm->d_kp) {
         HIP_OK(vm, hipMalloc(&vm->d_kp, sizeof(KParams) * mimic_vm::KP_SLOTS));
@@ -339,8 +338,8 @@ static int kp_slot(mimic_vm *vm, const KParams &kp, hipStream_t st, const KParam
         // Every launch from a slot records the slot's event on its own stream right behind the
         // kernel (run_xdp_impl): a slot is reused once that event has passed, whatever stream the
         // caller uses next -- no device-wide wait when the caller changes streams, no reference to
-        // a stream the caller may have destroyed.  Only the interpreter and MIMIC_JIT_KARG=0 JIT
-        // kernels read their parameters from a slot; the hot JIT kernels take them by value.
+        // a stream the caller may have destroyed.  Only the batch interpreter reads its
+        // parameters from a slot; JIT kernels take them by value.
         slot = vm->kp_next;
         vm->kp_next = (slot + 1) % mimic_vm::KP_SLOTS;
         if (vm->kp_used[slot]) HIP_OK(vm, hipEventSynchronize(vm->kp_ev[slot]));  // its last kernel is done
@@ -1823,7 +1822,7 @@ struct SkbInto {
 };
 static int skb_ensure(mimic_vm *vm, uint32_t n, hipStream_t st);
 static int skb_prepare(mimic_vm *vm, const mimic_xdp_batch *b, hipStream_t st, const SkbInto *into = nullptr,
-                       bool records = true, bool sparse = false, uint32_t *rooms_state = nullptr) {
+                       uint32_t *rooms_state = nullptr) {
     const uint32_t n = b->n;
     if (vm->skb_stream && vm->skb_stream != st) HIP_OK(vm, hipStreamSynchronize(vm->skb_stream));
     // batches released on a stream the caller may have destroyed since: ordered through their event
@@ -1833,15 +1832,10 @@ static int skb_prepare(mimic_vm *vm, const mimic_xdp_batch *b, hipStream_t st, c
     // the first leak follows the stack and sk_buff entries: St + S + 1 + 193
     const uint64_t init = (uint64_t)vm->next_addr + stack_size(vm) + 1 + SKB_STRUCT_SIZE + 1;
     // a batch's derived words go to the compact array (read by skb_load*), a process's into its record
-    uint64_t *out = into ? (uint64_t *)into->rec : records ? vm->d_skb_drv : nullptr;
+    uint64_t *out = into ? (uint64_t *)into->rec : vm->d_skb_drv;
     const uint32_t out_q = into ? (uint32_t)(sizeof(SkbRec) / 8) : SKB_DERIVED_Q;
-    // MIMIC_SKB_ROOMS_CHAIN=1 (measurement, JIT batches only): the chain kernel reads the rooms itself
-    static const bool rooms_chain = getenv("MIMIC_SKB_ROOMS_CHAIN") && getenv("MIMIC_SKB_ROOMS_CHAIN")[0] == '1';
-    // MIMIC_SKB_ROOMS_ZERO=1: the prep zeroes every loaded packet's rooms without reading them
-    static const bool rooms_zero = getenv("MIMIC_SKB_ROOMS_ZERO") && getenv("MIMIC_SKB_ROOMS_ZERO")[0] == '1';
     if (mimic_launch_skb_prep(b->pkt_data, b->pkt_off, b->pkt_len, n, out, out_q, into ? into->prefix : vm->d_skb_prefix,
-                              vm->d_skb_state, init, vm->skb_leaked ? 0u : 1u, (rooms_chain && !into) ? 0u : rooms_zero ? 2u : 1u,
-                              (sparse && !into) ? 1u : 0u, into ? nullptr : rooms_state, st))
+                              vm->d_skb_state, init, vm->skb_leaked ? 0u : 1u, into ? nullptr : rooms_state, st))
         return fail(vm, MIMIC_EDEVICE, "sk_buff prep: %s", hipGetErrorString(hipGetLastError()));
     if (n) vm->skb_leaked = true;
     vm->skb_stream = st;
@@ -2309,7 +2303,7 @@ static int run_xdp_impl(mimic_vm *vm, uint32_t prog_id, const mimic_xdp_batch *b
                         : cxk ? vm->jit_info_cx[ctx] : vm->jit_info[ctx];
     hipFunction_t jfn = proc_jit ? vm->jit_fn_proc : own ? vm->jit_fn_spread_own : spread ? vm->jit_fn_spread
                         : cxk ? vm->jit_fn_cx[ctx] : vm->jit_fn[ctx];
-    if (proc_jit && (!jfn || !ji.proc_ok || !ji.karg)) return fail(vm, MIMIC_EDEVICE, "process: no single-process JIT kernel (engine)");
+    if (proc_jit && (!jfn || !ji.proc_ok)) return fail(vm, MIMIC_EDEVICE, "process: no single-process JIT kernel (engine)");
     uint32_t run_lanes = lanes;
     if (spread) {
         // owned: 256 / P vCPU lanes per block
@@ -2353,7 +2347,6 @@ static int run_xdp_impl(mimic_vm *vm, uint32_t prog_id, const mimic_xdp_batch *b
             kp.spread_part = vm->d_spread_part;
         }
     }
-    kp.skb_rec_built = 1;
     if (skb && step && step->skb_rec) {   // a stepped sk_buff process: Load ran at NewProcess
         kp.ctx_kind = CTX_SKB;
         kp.skb_ifindex = skb->ifindex;
@@ -2373,17 +2366,13 @@ static int run_xdp_impl(mimic_vm *vm, uint32_t prog_id, const mimic_xdp_batch *b
         kp.skb_custom = skb->custom;
         vm->skb_stream = st;
     } else if (skb) {
-        // a JIT kernel that walks the headers itself needs the footprints only; one that derives the
-        // common frames' records itself (skb_load_fast): exception records only
-        const bool own_recs = jit && ji.skb_walk, sparse = jit && ji.skb_fast;
-        rc = skb_prepare(vm, b, st, nullptr, !own_recs, sparse, skb->rooms_state);
+        rc = skb_prepare(vm, b, st, nullptr, skb->rooms_state);
         if (rc) return rc;
         kp.skb_rooms_state = skb->rooms_state;
-        kp.skb_rec_built = own_recs ? 0u : sparse ? 2u : 1u;
         kp.ctx_kind = CTX_SKB;
         kp.skb_ifindex = skb->ifindex;
         kp.skb_rec = vm->d_skb_rec;
-        kp.skb_drv = own_recs ? nullptr : vm->d_skb_drv;
+        kp.skb_drv = vm->d_skb_drv;
         kp.skb_prefix = vm->d_skb_prefix;
         kp.skb_base = vm->d_skb_state + 1;
         kp.skb_custom = skb->custom;
@@ -2450,8 +2439,8 @@ static int run_xdp_impl(mimic_vm *vm, uint32_t prog_id, const mimic_xdp_batch *b
                                       mr->r[q].steps, mr->r[q].err_pc, 0};
         }
     }
-    if (jit && ji.karg) {  // launch parameters by value: the runtime copies them into the kernarg segment
-        if (mimic_jit_launch(jfn, ji, &kp, nullptr, st))
+    if (jit) {  // launch parameters by value: the runtime copies them into the kernarg segment
+        if (mimic_jit_launch(jfn, &kp, st))
             return fail(vm, MIMIC_EDEVICE, "launch: %s", hipGetErrorString(hipGetLastError()));
         // the interpreter finishes what the kernel deferred (a wave without a deferred lane returns at once)
         if (ji.defer && mimic_launch_xdp_resume(&kp, st))
@@ -2459,13 +2448,11 @@ static int run_xdp_impl(mimic_vm *vm, uint32_t prog_id, const mimic_xdp_batch *b
     } else if (step) {   // the stepping kernel takes its parameters by value: no slot, no copy
         if (mimic_launch_xdp(&kp, nullptr, st))
             return fail(vm, MIMIC_EDEVICE, "launch: %s", hipGetErrorString(hipGetLastError()));
-    } else {  // launch parameters are read from a device copy
+    } else {  // the batch interpreter reads its launch parameters from a device copy
         const KParams *dkp = nullptr;
         const int slot = kp_slot(vm, kp, st, &dkp);
         if (slot < 0) return slot;
-        if (jit ? mimic_jit_launch(jfn, ji, &kp, dkp, st) : mimic_launch_xdp(&kp, dkp, st))
-            return fail(vm, MIMIC_EDEVICE, "launch: %s", hipGetErrorString(hipGetLastError()));
-        if (jit && ji.defer && mimic_launch_xdp_resume(&kp, st))
+        if (mimic_launch_xdp(&kp, dkp, st))
             return fail(vm, MIMIC_EDEVICE, "launch: %s", hipGetErrorString(hipGetLastError()));
         HIP_OK(vm, hipEventRecord(vm->kp_ev[slot], st));   // the slot is free again once this passes
         vm->kp_used[slot] = true;
@@ -2647,7 +2634,7 @@ static bool proc_jit_ready(mimic_vm *vm) {
         JitInfo ji{};
         hipFunction_t fn = nullptr;
         const std::string src = mimic_jit_source(vm->h_dp, vm->h_all, CTX_XDP, &ji, &vc, false, nullptr, false, true);
-        if (ji.proc_ok && ji.karg && !mimic_jit_compile(vm->s.device, src, &fn, &log)) {
+        if (ji.proc_ok && !mimic_jit_compile(vm->s.device, src, &fn, &log)) {
             vm->jit_fn_proc = fn;
             vm->jit_info_proc = ji;
             vm->proc_jit = 1;
@@ -3194,8 +3181,9 @@ long mimic_jit_source_for_ctx(const void *const *progs, const uint32_t *n_slots,
 
 long mimic_jit_source_vc(const void *const *progs, const uint32_t *n_slots, uint32_t n_progs, int32_t ctx_kind,
                          const uint32_t *vc_slots, uint32_t n_vc, char *buf, size_t cap) {
-    // (ctx_kind | 0x100: the single-process form of an xdp_md set, what Process.Run tiers up to)
-    const bool proc = (ctx_kind & 0x100) != 0;
+    // (ctx_kind | 0x100: the single-process form of an xdp_md set, what Process.Run tiers up to;
+    // | 0x200: the form without early packet loads, the engine's fallback when a 4-wave build spills)
+    const bool proc = (ctx_kind & 0x100) != 0, no_early_loads = (ctx_kind & 0x200) != 0;
     ctx_kind &= 0xff;
     if (ctx_kind != MIMIC_CTX_XDP && ctx_kind != MIMIC_CTX_SKB) return MIMIC_EINVAL;
     if (proc && ctx_kind != MIMIC_CTX_XDP) return MIMIC_EINVAL;
@@ -3213,7 +3201,7 @@ long mimic_jit_source_vc(const void *const *progs, const uint32_t *n_slots, uint
         if (p >= dp.size() || s >= dp[p].n) return MIMIC_EINVAL;
         vc.push_back({dp[p].base + s, rb});
     }
-    const std::string src = mimic_jit_source(dp, all, (uint32_t)ctx_kind, nullptr, &vc, false, nullptr, false, proc);
+    const std::string src = mimic_jit_source(dp, all, (uint32_t)ctx_kind, nullptr, &vc, no_early_loads, nullptr, false, proc);
     if (buf && cap > src.size()) memcpy(buf, src.c_str(), src.size() + 1);
     return (long)src.size();
 }

@@ -215,7 +215,7 @@ static __device__ __forceinline__ void xdp_body(const KParams *__restrict__ kpp,
         if (resumed || foreign) {
         } else if (i != 0xffffffffu && kp.ctx_kind == CTX_SKB) {   // LinuxContextSKBuff.Load (skb.h)
             uint64_t r1 = 0;
-            const int ls = skb_load<MODE == MODE_RESUME>(kp, L, i, r1, resume_here);
+            const int ls = skb_load(kp, L, i, r1, resume_here);
             REG(10) = kp.static_next + kp.frame_size;
             if (ls) {
                 TERM(ls, -1);
@@ -501,8 +501,6 @@ static __device__ __forceinline__ void xdp_body(const KParams *__restrict__ kpp,
 }
 
 extern "C" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void mimic_xdp_kernel(const KParams *__restrict__ kpp) { xdp_body<MODE_BATCH>(kpp); }
-// the same body at the compiler's own budget (3 waves per SIMD, no spills): MIMIC_INTERP_WAVES=3
-extern "C" __global__ __launch_bounds__(256) void mimic_xdp_kernel_w3(const KParams *__restrict__ kpp) { xdp_body<MODE_BATCH>(kpp); }
 // Process.Step / Run: launch parameters by value (no parameter slot, no copy ahead of the launch)
 extern "C" __global__ __launch_bounds__(256) void mimic_xdp_step_kernel(const KParams kp_arg) {
     (void)kp_arg;
@@ -666,7 +664,7 @@ static __device__ void hc_copy(uint8_t *base, uint32_t n, uint32_t s, uint32_t d
     }
 }
 #define HC_T 1024u   // threads per block
-extern "C" __global__ __launch_bounds__(HC_T) void mimic_hash_compact_kernel(uint8_t *arena, DMap m, uint32_t meas) {
+extern "C" __global__ __launch_bounds__(HC_T) void mimic_hash_compact_kernel(uint8_t *arena, DMap m) {
     const HT t = h_table(arena, m);
     HashCtl *c = h_ctl(t);
     const uint32_t cminv = c->cminv, fullf = c->full;
@@ -678,7 +676,7 @@ extern "C" __global__ __launch_bounds__(HC_T) void mimic_hash_compact_kernel(uin
     const uint32_t hi = hd < E ? (uint32_t)hd : E;
     uint32_t lo = cminv ? 0xffffffffu - cminv : hi;
     lo = lo < hi ? lo : hi;
-    const uint32_t w0 = lo >> 5, nw = (meas & 8u) ? 0u : ((hi + 31u) >> 5) - w0;
+    const uint32_t w0 = lo >> 5, nw = ((hi + 31u) >> 5) - w0;
     const uint8_t *used = h_used8(t);
     // the used bytes as bit words (plain loads: the launch that wrote them has ended), below lo
     // counted as used, from hi on as free.  Every load of the thread first (indices clamped, no
@@ -735,7 +733,7 @@ extern "C" __global__ __launch_bounds__(HC_T) void mimic_hash_compact_kernel(uin
     const uint32_t Sm = (mw < nw ? pf[mw] : T) + (mw < nw && mb ? (uint32_t)__builtin_popcount(wd[mw] & ((1u << mb) - 1u)) : 0u);
     const uint32_t H = T - Sm;   // movers = holes
     uint8_t *kb = arena + m.keys_dev_off, *vb = arena + m.dev_off;
-    for (uint32_t r = blockIdx.x * HC_T + threadIdx.x; r < ((meas & 1u) ? 0u : H); r += gridDim.x * HC_T) {
+    for (uint32_t r = blockIdx.x * HC_T + threadIdx.x; r < H; r += gridDim.x * HC_T) {
         // the mover: the (Sm + r)-th used slot; the hole: the r-th free slot (zeros before word i: 32 i - pf[i])
         const uint32_t j = Sm + r;
         uint32_t a = 0, b = nw;   // the last word with pf <= j
@@ -758,7 +756,7 @@ extern "C" __global__ __launch_bounds__(HC_T) void mimic_hash_compact_kernel(uin
     }
     // ring positions [lo, m) popped (every block a share: nothing in this kernel reads the ring)
     int32_t *ring = h_ring(t);
-    for (uint32_t q = lo + blockIdx.x * HC_T + threadIdx.x; q < ((meas & 2u) ? lo : mm); q += gridDim.x * HC_T) ring[q] = -1;
+    for (uint32_t q = lo + blockIdx.x * HC_T + threadIdx.x; q < mm; q += gridDim.x * HC_T) ring[q] = -1;
     // The last block to get here clears what every block has read (their reads are complete: each
     // block used the values before counting itself).  No fence: nothing written here is read back in
     // this kernel, and the kernel's end publishes it (a release fence per block -- an L2 write-back
@@ -771,7 +769,7 @@ extern "C" __global__ __launch_bounds__(HC_T) void mimic_hash_compact_kernel(uin
     typedef uint32_t u32x4z __attribute__((ext_vector_type(4)));
     u32x4z *uz = (u32x4z *)(h_used8(t) + ((size_t)w0 << 5));
     const u32x4z z4 = {0, 0, 0, 0};
-    for (uint32_t i = threadIdx.x; i < ((meas & 4u) ? 0u : 2 * nw); i += HC_T) uz[i] = z4;
+    for (uint32_t i = threadIdx.x; i < 2 * nw; i += HC_T) uz[i] = z4;
     unsigned long long *left = h_left(t);
     const uint32_t nl = c->nleft < HT_LEFT_CAP ? c->nleft : HT_LEFT_CAP;
     for (uint32_t q = threadIdx.x; q < nl; q += HC_T) left[q] = 0;
@@ -788,13 +786,9 @@ extern "C" __global__ __launch_bounds__(HC_T) void mimic_hash_compact_kernel(uin
 
 extern "C" int mimic_launch_hash_compact(uint8_t *arena, const DMap *m, hipStream_t st) {
     // every block scans all bit words (<= 4096), then takes a share of the movers: about a mover per
-    // thread (MIMIC_COMPACT_BLOCKS=n: n blocks, measurement)
-    static const uint32_t forced = [] { const char *e = getenv("MIMIC_COMPACT_BLOCKS"); return e ? (uint32_t)atoi(e) : 0u; }();
-    const uint32_t blocks = forced ? forced : std::min<uint32_t>(64u, std::max<uint32_t>(1u, m->max_entries / 4096u));
-    // MIMIC_COMPACT_MEAS (measurement only, results wrong): 1 no moves, 2 no ring writes, 4 no clearing
-    // of the used bytes, 8 no scan (nothing found)
-    static const uint32_t meas = [] { const char *e = getenv("MIMIC_COMPACT_MEAS"); return e ? (uint32_t)atoi(e) : 0u; }();
-    hipLaunchKernelGGL(mimic_hash_compact_kernel, dim3(blocks), dim3(HC_T), 0, st, arena, *m, meas);
+    // thread
+    const uint32_t blocks = std::min<uint32_t>(64u, std::max<uint32_t>(1u, m->max_entries / 4096u));
+    hipLaunchKernelGGL(mimic_hash_compact_kernel, dim3(blocks), dim3(HC_T), 0, st, arena, *m);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -875,9 +869,7 @@ extern "C" int mimic_launch_xdp_resume(const KParams *kp, hipStream_t st) {
 extern "C" int mimic_launch_xdp(const KParams *kp, const KParams *d_kp, hipStream_t st) {
     const uint32_t blocks = (kp->lanes + 255) / 256;
     if (blocks == 0) return 0;
-    static const bool w3 = [] { const char *e = getenv("MIMIC_INTERP_WAVES"); return e && e[0] == '3'; }();
     if (kp->step) hipLaunchKernelGGL(mimic_xdp_step_kernel, dim3(blocks), dim3(256), (size_t)kp->step_ins_n * sizeof(DInsn), st, *kp);
-    else if (w3) hipLaunchKernelGGL(mimic_xdp_kernel_w3, dim3(blocks), dim3(256), 0, st, d_kp);
     else hipLaunchKernelGGL(mimic_xdp_kernel, dim3(blocks), dim3(256), 0, st, d_kp);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -77,90 +77,41 @@ int64_t jump_target(const DInsn &x, int64_t i) {
     return insn_op(x) == 0x85 ? i + (int64_t)(int32_t)(uint32_t)x.k : i + insn_off(x) + 1;
 }
 
+// environment knobs: off() unless the variable is 0, on() when it is 1, num() its value
+bool off(const char *name) { const char *v = getenv(name); return !(v && v[0] == '0'); }
+bool on(const char *name) { const char *v = getenv(name); return v && v[0] == '1'; }
+int num(const char *name, int dflt) { const char *v = getenv(name); return v ? atoi(v) : dflt; }
+
 class Gen {
   public:
     Gen(const std::vector<ProgView> &progs, uint32_t ctx_kind) : P(progs), ctx(ctx_kind) {
         // tuning knobs (environment; they change the generated source, hence the cache key)
-        const char *f = getenv("MIMIC_JIT_FAST");
-        fast_paths = !(f && f[0] == '0');
-        // MIMIC_JIT_KQ: which once-per-packet KParams fields are read through an opaque pointer
-        // (0 none: hoisted into SGPRs; 1 all; 2 the result pointers only).  Measured on MI355X
-        // (cfg 2): 0 = 44.6 us per launch, 1 and 2 = 52-54 us -- a scalar load in front of every
-        // packet's result stores costs more than the couple of SGPRs spilled into VGPR lanes.
-        const char *kq = getenv("MIMIC_JIT_KQ");
-        kq_mode = kq ? atoi(kq) : 0;
-        // MIMIC_JIT_NT=1: non-temporal packet / descriptor / result accesses.  Measured slower on
-        // MI355X (cfg 2: 48 us vs 37 us per launch): a packet is read by several small loads, and
-        // evict-first lines make the later ones miss.
-        const char *ntv = getenv("MIMIC_JIT_NT");
-        nt = ntv && ntv[0] == '1';
-        const char *pfv = getenv("MIMIC_JIT_PREFETCH");   // 0: no descriptor prefetch
-        prefetch = !(pfv && pfv[0] == '0');
-        const char *xv = getenv("MIMIC_JIT_XPF");   // 1: next-packet header window prefetch
-        xpf_knob = xv && xv[0] == '1';
-        const char *lpv = getenv("MIMIC_JIT_LPF");   // 1: lane-start prefetch of the first packets' windows
-        lpf_knob = lpv && lpv[0] == '1';
-        const char *hv = getenv("MIMIC_JIT_HINT");   // 1: [[unlikely]] on the slow-path branches (measured: no change)
-        hint_knob = hv && hv[0] == '1';
-        const char *lq = getenv("MIMIC_JIT_LDSSTK");   // 8-byte words of the LDS stack window (0: none)
-        if (lq) lds_stack_q = (uint32_t)std::min(32, std::max(0, atoi(lq)));
-        const char *dv = getenv("MIMIC_JIT_DISPATCH");   // 0: a jump table at every tail-call site
-        dispatch_knob = !(dv && dv[0] == '0');
-        const char *vcv = getenv("MIMIC_JIT_VC");   // 0: no lane value cache
-        vc_knob = !(vcv && vcv[0] == '0');
-        const char *fw = getenv("MIMIC_JIT_FWD");   // 0: no stack-store -> lookup key forwarding
-        forward = !(fw && fw[0] == '0');
-        const char *ka = getenv("MIMIC_JIT_KARG");   // 0: launch parameters through a device copy (slots)
-        if (ka) karg = atoi(ka);
-        const char *nr = getenv("MIMIC_JIT_NTRES");   // 0: per-packet results stored as plain stores
-        ntres = !(nr && nr[0] == '0');
-        const char *cbv = getenv("MIMIC_JIT_COMBINE");
-        combine_knob = !(cbv && cbv[0] == '0');
-        const char *hcv = getenv("MIMIC_JIT_HCHUNK");   // 0: no chunked reservations; N: chunks of up to N positions
-        if (hcv) hchunk_knob = atoi(hcv);
-        const char *dnr = getenv("MIMIC_JIT_DEFER_NOREGS");
-        defer_noregs = dnr ? atoi(dnr) : 0;
-        const char *sf = getenv("MIMIC_JIT_SKBFIELD");   // 0: sk_buff fields through the generic convertAccess
-        skb_fields = !(sf && sf[0] == '0');
-        const char *sl = getenv("MIMIC_JIT_SKBLDS");   // 0: sk_buff records read from global memory
-        skb_lds_knob = !(sl && sl[0] == '0');
-        const char *sw = getenv("MIMIC_JIT_SKBWALK");   // 1: the kernel builds its sk_buff records (measured slower)
-        skb_walk_knob = sw && sw[0] == '1';
-        const char *sfa = getenv("MIMIC_JIT_SKBFAST");   // 1: common frames' records derived in the kernel
-        skb_fast_knob = sfa && sfa[0] == '1';
-        const char *stc = getenv("MIMIC_JIT_SKBTOUCH");   // 0: no next-descriptor prefetch / header touch
-        skb_touch_knob = stc ? (uint32_t)atoi(stc) : 0u;   // 1: prefetch + touch, 2: the offset prefetch only
-        const char *sml = getenv("MIMIC_JIT_SMLDS");
-        sm_lds_knob = !(sml && sml[0] == '0');
-        const char *ic = getenv("MIMIC_JIT_INC");   // 0: counter increments as three slots
-        inc_knob = !(ic && ic[0] == '0');
-        const char *hf = getenv("MIMIC_JIT_HASH");   // 0: hash-map lookups always through the generic helper
-        hash_fast = !(hf && hf[0] == '0');
-        const char *rd = getenv("MIMIC_JIT_RETDISPATCH");   // BPF-to-BPF returns through one block per program
-        ret_dispatch = rd ? rd[0] == '1' : !fast_paths;     // (default: in kernels without fast paths)
-        const char *ti = getenv("MIMIC_JIT_TAIL");   // 0: tail calls always through the generic helper
-        tail_inline = !(ti && ti[0] == '0');
-        const char *ce = getenv("MIMIC_JIT_CENSUS");   // 1: per-packet slow-path call counts in place of steps
-        census = ce && ce[0] == '1';
-        const char *mt = getenv("MIMIC_JIT_MEMTIME");   // 1: per-packet start / end clocks in place of steps / err_pc
-        memtime = mt && mt[0] == '1';
-        const char *el = getenv("MIMIC_JIT_ELIDE");   // 0: forwarded key stores are always made
-        elide = !(el && el[0] == '0');
-        const char *wnd = getenv("MIMIC_JIT_WINDOW");   // 0: early loads one by one
-        window = !(wnd && wnd[0] == '0');
-        const char *spv = getenv("MIMIC_JIT_SPEC");   // 0: no early packet loads
-        if (spv) speculate = atoi(spv);
-        const char *wv = getenv("MIMIC_JIT_WAVES");   // minimum waves per SIMD the register budget targets
-        if (wv) waves = atoi(wv);
-        const char *ol = getenv("MIMIC_JIT_OPAQUE_LANE");
-        opaque_lane = ol && ol[0] == '1';
-        const char *cm = getenv("MIMIC_JIT_COLD");   // call | inline (default: by kernel size)
+        // (each knob's meaning is next to its member below; DESIGN.md lists them all)
+        fast_paths = off("MIMIC_JIT_FAST");
+        prefetch = off("MIMIC_JIT_PREFETCH");
+        xpf_knob = on("MIMIC_JIT_XPF");
+        lpf_knob = on("MIMIC_JIT_LPF");
+        lds_stack_q = (uint32_t)std::min(32, std::max(0, num("MIMIC_JIT_LDSSTK", 16)));
+        dispatch_knob = off("MIMIC_JIT_DISPATCH");
+        vc_knob = off("MIMIC_JIT_VC");
+        forward = off("MIMIC_JIT_FWD");
+        ntres = off("MIMIC_JIT_NTRES");
+        combine_knob = off("MIMIC_JIT_COMBINE");
+        hchunk_knob = num("MIMIC_JIT_HCHUNK", 32);
+        skb_fields = off("MIMIC_JIT_SKBFIELD");
+        skb_lds_knob = off("MIMIC_JIT_SKBLDS");
+        sm_lds_knob = off("MIMIC_JIT_SMLDS");
+        inc_knob = off("MIMIC_JIT_INC");
+        hash_fast = off("MIMIC_JIT_HASH");
+        ret_dispatch = getenv("MIMIC_JIT_RETDISPATCH") ? on("MIMIC_JIT_RETDISPATCH") : !fast_paths;
+        tail_inline = off("MIMIC_JIT_TAIL");
+        census = on("MIMIC_JIT_CENSUS");
+        elide = off("MIMIC_JIT_ELIDE");
+        window = off("MIMIC_JIT_WINDOW");
+        speculate = num("MIMIC_JIT_SPEC", 8);
+        waves = num("MIMIC_JIT_WAVES", 0);
+        const char *cm = getenv("MIMIC_JIT_COLD");
         cold_mode = !cm ? 0 : !strcmp(cm, "call") ? 1 : !strcmp(cm, "inline") ? 2 : !strcmp(cm, "defer") ? 3 : 0;
-        // MIMIC_JIT_STAGE=1: stage each packet's first 64 bytes in LDS.  Measured slower on MI355X
-        // for every config (cfg 2: 74 us vs 37 us, cfg 3: 2.6 ms vs 1.2 ms per launch): the staging
-        // waits for all eight qwords before the first use, while direct loads hit L1 / L2 anyway.
-        const char *sg = getenv("MIMIC_JIT_STAGE");
-        stage = sg && sg[0] == '1';
         for (auto &p : P)
             for (uint32_t i = 0; i < p.n; i++) {
                 const DInsn &x = p.ins[i];
@@ -191,35 +142,12 @@ class Gen {
     uint32_t max_n = 0;
     bool fast_paths = true;    // MIMIC_JIT_FAST=0: every access through resolve()
     int cold_mode = 0;         // MIMIC_JIT_COLD: 0 auto, 1 call, 2 inline, 3 defer
-    int kq_mode = 0;           // per-packet KParams fields through an opaque pointer (see MIMIC_JIT_KQ)
-    bool opaque_lane = false;  // per-iteration opaque lane index (MIMIC_JIT_OPAQUE_LANE=1)
-    bool nt = false;           // MIMIC_JIT_NT=1: streaming accesses non-temporal
     bool skb_fields = true;    // MIMIC_JIT_SKBFIELD=0: no per-field sk_buff access code
     bool skb_lds_knob = true;  // MIMIC_JIT_SKBLDS=0: no LDS copy of the sk_buff record
     bool skb_lds = false;
-    // the kernel runs SKBuffFromBytes itself into the LDS slot (skb_load_walk), over a 128-byte
-    // header window per thread in LDS: the prep kernel then writes footprints only
-    // (MIMIC_JIT_SKBWALK=1; measured slower on MI355X: cfg 5 0.447 -> 0.482 ms per step at
-    // V = 128K -- the walk on the chain's critical path costs more than the record round trip)
-    bool skb_walk_knob = false;
-    bool skb_walk = false;
-    // the kernel derives the record of every frame skb_fast takes from the packet's first bytes
-    // (skb_load_fast); the prep kernel writes records for the other frames only (sparse prep)
-    bool skb_fast_knob = false;   // (measured slower on MI355X: DESIGN.md 6.1)
-    bool skb_fast = false;
-    // sk_buff kernels (prep records in LDS), MIMIC_JIT_SKBTOUCH=1/2: the next packet's offset is loaded
-    // while the current one runs, and (1) a packet's header lines are touched when its record load is
-    // issued, so the programs' LD_ABS / direct packet loads find them in L2.  Off: the cfg-5 chain sits
-    // at 255 VGPRs, and either form takes it to 256 + 2 AGPRs -- one wave per SIMD, 0.22 -> 0.36 ms
-    // (profiles/r05/)
-    uint32_t skb_touch_knob = 0;
-    bool skb_touch = false;
     bool inc_knob = true;      // MIMIC_JIT_INC=0: no fused counter increments (fusable_inc)
     bool sm_lds_knob = true;   // MIMIC_JIT_SMLDS=0: stack validity masks in VGPRs in defer mode too
     static constexpr uint32_t kSrecQ = 21;   // 8-byte words per LDS record slot (SkbRec is 20)
-    int karg = 2;              // MIMIC_JIT_KARG: 2 launch parameters by value in the kernarg segment, read
-                               // through an opaque constant-space pointer; 1 the same, plain; 0 a
-                               // pointer to a device copy (a copy + event per new batch between kernels)
     bool hash_fast = true;     // MIMIC_JIT_HASH=0: no inline hash-map lookups
     bool tail_inline = true;   // MIMIC_JIT_TAIL=0: no inline tail calls
     // An EXIT that pops a frame goes to its program's one return block (R<p>_) instead of carrying the
@@ -230,13 +158,9 @@ class Gen {
     // D_ exists for the same kind of control flow.  MIMIC_JIT_RETDISPATCH=1 / 0: everywhere / nowhere.
     bool ret_dispatch = false;
     bool census = false;       // MIMIC_JIT_CENSUS=1: diagnostics (tools/cold_census.py)
-    // MIMIC_JIT_MEMTIME=1 (measurement only, tools/memtime.py): s_memrealtime (100 MHz) when each
-    // packet's process starts (err_pc) and when its results are stored (steps)
-    bool memtime = false;
     bool elide = true;         // MIMIC_JIT_ELIDE=0: no deferred stack stores
     bool window = true;        // MIMIC_JIT_WINDOW=0: no windowed early loads
     int speculate = 8;         // MIMIC_JIT_SPEC=N: at most N early packet loads per region (0: none)
-    int defer_noregs = 0;   // MIMIC_JIT_DEFER_NOREGS=1: deferral sites store no registers, 2: low halves (register census only)
     bool combine_knob = true;  // MIMIC_JIT_COMBINE=0: every wave reserves freelist positions with its own add
     bool hash_combine = false;
     int hchunk_knob = 32;       // MIMIC_JIT_HCHUNK (hashmap.h MIMIC_HCHUNK; 0: off)
@@ -252,10 +176,9 @@ class Gen {
     // independent but for per-CPU state, which the programs keep in the lane value cache or in
     // memory they do not prefetch).  Only for program sets that never store into packet memory.
     // Off by default: cfg 2 measured 25.6 -> 32.0 us per launch (the lanes' prologue burst of 1 M
-    // descriptor and window loads delays every first packet; tools/memtime.py), the
+    // descriptor and window loads delays every first packet), the
     // chunked schedule 38.9 -> 36.8 us, cfg 3 / cfg 4 unchanged.
     bool lpf_knob = false;
-    bool hint_knob = false;    // MIMIC_JIT_HINT=1: slow-path branches marked [[unlikely]] (laid out after the hot code)
     bool lpf_on = false;
     bool lds_stack_on = false;
     static constexpr uint32_t kLpfD = 4;
@@ -296,7 +219,6 @@ class Gen {
     std::vector<std::vector<uint16_t>> live;   // [prog][slot]: registers live into the slot
     uint32_t cold_sites = 0;
     static constexpr uint32_t kColdInlineSites = 48;
-    bool stage = false;        // MIMIC_JIT_STAGE=1: LDS packet window
     bool has_tail() const { return any_tail; }
     bool has_early_loads() const { return !spec_use.empty(); }
     // Tail calls jump between programs.  With a jump table at every tail-call site as well as at
@@ -315,21 +237,6 @@ class Gen {
     uint32_t ctx = CTX_XDP;    // the batch context this kernel is generated for
 
     std::string source() {
-        // stage packets in LDS only when some access is expected to hit the packet
-        if (stage) {
-            bool any = false;
-            for (auto &p : P) {
-                ctx_hints(p);
-                for (uint32_t i = 0; i < p.n; i++) {
-                    const DInsn &x = p.ins[i];
-                    const uint32_t h = AUX_H(x.aux);
-                    if (h == H_LDX && hint(insn_src(x)) == HINT_PKT) any = true;
-                    if ((h == H_ST || h == H_STX) && hint(insn_dst(x)) == HINT_PKT) any = true;
-                    if (h == H_LDABS && ctx == CTX_SKB) any = true;
-                }
-            }
-            stage = any && fast_paths;
-        }
         // cold paths: inlined at each site for small kernels (best register allocation), called
         // for large ones (hipRTC time grows with every inlined copy)
         uint32_t sites = 0;
@@ -342,14 +249,14 @@ class Gen {
         cold_sites = sites;
         // (the single-process form calls its slow paths: one lane, and hipRTC time is its tier-up cost)
         cold_inline = !proc && (cold_mode == 2 || (cold_mode == 0 && sites <= kColdInlineSites));
-        defer_mode = !cold_inline && (cold_mode == 3 || cold_mode == 0) && !census && !stage && fast_paths && !proc;
+        defer_mode = !cold_inline && (cold_mode == 3 || cold_mode == 0) && !census && fast_paths && !proc;
         if (fast_paths) analyze_live();
         analyze_vc();
         if (forward)
             for (auto &p : P) analyze_fwd(p);
         if (forward && elide)
             for (auto &p : P) analyze_elide(p);
-        if (speculate && fast_paths && !stage && !all_leaders)
+        if (speculate && fast_paths && !all_leaders)
             for (auto &p : P) analyze_spec(p);
         spread_on = analyze_spread();
         spread_own = spread_on && spread_req->own;
@@ -371,7 +278,6 @@ class Gen {
             lds_stack_on = any;
         }
         if (defer_mode && sm_lds_knob) E.line("#define MIMIC_SM_LDS 1");
-        if (const char *rm = getenv("MIMIC_JIT_ROOMS")) E.line("#define MIMIC_ROOMS_MODE %d", atoi(rm));   // measurement knob
         if (const char *dv = getenv("MIMIC_JIT_DEFS")) {   // measurement knob: "A,B=2" -> #define A / #define B 2
             std::string all(dv), d;
             for (size_t a = 0; a <= all.size(); a++) {
@@ -381,14 +287,11 @@ class Gen {
                 d.clear();
             }
         }
-        // traffic-attribution knobs (set through MIMIC_JIT_DEFS; results are wrong with them on):
-        // no packet stores on the fast path, no fused counter adds, no per-packet result stores
-        E.line("#ifdef MIMIC_MEAS_NOPKTST\n#define PKT_ST(p_, n_, v_) ((void)(v_))\n#else\n#define PKT_ST(p_, n_, v_) st_n(p_, n_, v_)\n#endif");
-        E.line("#ifdef MIMIC_MEAS_NOATOM\n#define CNT_ADD(p_, n_, v_) ((void)(p_))\n#else\n#define CNT_ADD(p_, n_, v_) atomic_add_n(p_, n_, v_)\n#endif");
+        // a packet store on the fast path; a fused counter add (fusable_inc)
+        E.line("#define PKT_ST(p_, n_, v_) st_n(p_, n_, v_)");
+        E.line("#define CNT_ADD(p_, n_, v_) atomic_add_n(p_, n_, v_)");
         if (spread_on) E.line("#define MIMIC_SPREAD 1");
         if (spread_own) E.line("#define MIMIC_SPREAD_OWN 1");
-        if (const char *rc = getenv("MIMIC_SKB_ROOMS_CHAIN"))   // measurement: see engine.cpp skb_prepare
-            if (rc[0] == '1') E.line("#define MIMIC_SKB_ROOMS_CHAIN 1");
         E.line("#define MIMIC_CTX_FIXED %u", ctx);
         E.line("#define MIMIC_COLD_INLINE %d", cold_inline ? 1 : 0);
         {   // no program of the set updates or deletes: hash tables are read-only in every launch
@@ -442,10 +345,7 @@ class Gen {
         E.line("#define FILL() do { r0 = sp_.r[0]; r1 = sp_.r[1]; r2 = sp_.r[2]; r3 = sp_.r[3]; r4 = sp_.r[4]; r5 = sp_.r[5]; "
                "L.sm0 = sp_.L.sm0; L.sm1 = sp_.L.sm1; L.xdp_dirty = sp_.L.xdp_dirty; L.t_lo = sp_.L.t_lo; L.t_n = sp_.L.t_n; "
                "L.t_ptr = sp_.L.t_ptr; } while (0)");
-        if (getenv("MIMIC_JIT_NOCOLD") && getenv("MIMIC_JIT_NOCOLD")[0] == '1')   // measurement only: no slow paths
-            E.line("#define COLD_CALL(call_, pc_) TERM(MIMIC_ERR_ENGINE_HELPER, pc_)");
-        else
-            E.line("#define COLD_CALL(call_, pc_) do { VC_FLUSH(); SPILL(); call_; FILL(); if (sp_.st) TERM(sp_.st, pc_); } while (0)");
+        E.line("#define COLD_CALL(call_, pc_) do { VC_FLUSH(); SPILL(); call_; FILL(); if (sp_.st) TERM(sp_.st, pc_); } while (0)");
         // defer mode: the site stored the live registers; the rest is the lane's (defer_finish)
         // (the lane value cache is written back once, at L_defer: not inlined at every site)
         E.line("#define DFR(pc_, prog_) do { dr_->pc = (int32_t)(pc_); dr_->prog = (prog_); dr_->steps = steps - 1u; goto L_defer; } while (0)");
@@ -456,47 +356,29 @@ class Gen {
             E.line("#define VC_FLUSH() do { if (vcd_) { vc_writeback(vcp_, vcb_, vc0_, vc1_, vc2_, vc3_); vcd_ = 0u; } vcv_ = 0u; } while (0)");
         else
             E.line("#define VC_FLUSH() do { } while (0)");
-        // KParams is read through a pointer to a device copy: fields are loaded (scalar) where
-        // they are used instead of all being preloaded into SGPRs from the kernarg segment
-        // (which spills SGPRs and costs VGPRs / occupancy)
         // Register budget: kernels small enough to inline their slow paths are built for 4 waves
         // per SIMD -- 262 144 lanes then run in one round on the 1 024 SIMDs.  cfg 4 (169 VGPRs,
         // 2 waves): 0.172 -> 0.137 ms per launch; cfg 2 and 3 fit 4 waves anyway.  Large kernels
         // (cfg 5) keep the compiler's choice: forcing 2 waves there spills 264 VGPRs (1.2 vs 0.7 ms).
         const int wv = proc ? 0 : waves > 0 ? waves : (cold_inline ? 4 : 0);
-        const std::string param = karg ? "const KParams kp_arg_" : "const KParams *__restrict__ kpp";
-        if (wv > 0)
-            E.line("%s", (std::string("extern \"C\" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(") +
-                          std::to_string(wv) + "))) void mimic_jit_kernel(" + param + ") {").c_str());
-        else
-            E.line("%s", ("extern \"C\" __global__ __launch_bounds__(256) void mimic_jit_kernel(" + param + ") {").c_str());
-        if (karg == 2) {
-            // the parameters stay in the kernarg segment (constant address space): an opaque
-            // constant-space pointer keeps every field a scalar load where it is used (not all
-            // preloaded into SGPRs at entry)
-            E.line("  (void)kp_arg_;   // the first (only) kernel argument: at offset 0 of the kernarg segment");
-            E.line("  const KParams __attribute__((address_space(4))) *kp4_ = (const KParams __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr();");
-            E.line("  asm volatile(\"\" : \"+s\"(kp4_));");
-            E.line("  const KParams *kpp = (const KParams *)kp4_;");
-        } else if (karg == 1) {
-            E.line("  const KParams *kpp = &kp_arg_;");
-        }
+        E.line("extern \"C\" __global__ __launch_bounds__(256) %svoid mimic_jit_kernel(const KParams kp_arg_) {",
+               wv > 0 ? ("__attribute__((amdgpu_waves_per_eu(" + std::to_string(wv) + "))) ").c_str() : "");
+        // the parameters stay in the kernarg segment (constant address space): an opaque
+        // constant-space pointer keeps every field a scalar load where it is used (not all
+        // preloaded into SGPRs at entry)
+        E.line("  (void)kp_arg_;   // the first (only) kernel argument: at offset 0 of the kernarg segment");
+        E.line("  const KParams __attribute__((address_space(4))) *kp4_ = (const KParams __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr();");
+        E.line("  asm volatile(\"\" : \"+s\"(kp4_));");
+        E.line("  const KParams *kpp = (const KParams *)kp4_;");
         E.line("  const KParams &kp = *kpp;");
         E.line("  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;");
         if (hash_chunk) E.line("  h_chunk_init(%s);   // (its waves: those the early return below keeps)", spread_on ? "0xffffffffu" : "kp.lanes");
         if (hash_combine) E.line("  h_comb_init();   // before any thread of the block can leave");
         if (!spread_on) E.line("  if (g >= kp.lanes) return;");
-        if (stage && fast_paths) {
-            E.line("  __shared__ PWin pwin_;");
-            E.line("  const uint32_t tl0_ = threadIdx.x;");
-        }
         skb_lds = ctx == CTX_SKB && fast_paths && skb_fields && skb_lds_knob;
         // the sk_buff records of the block's lanes, 168 bytes apart (an odd number of 8-byte
         // words: lanes reading the same field hit different banks); nothing reads them back
         if (skb_lds) E.line("  __shared__ uint64_t srec_[%uu * 256u];", kSrecQ);
-        skb_walk = skb_lds && skb_walk_knob;
-        skb_fast = skb_lds && !skb_walk && skb_fast_knob;
-        if (skb_walk) E.line("  __shared__ uint32_t swin_[(SKB_WIN / 4u) * 256u];   // header windows (skb_load_walk)");
         E.line("  Lane L;");
         E.line("  Spill sp_;");
         if (census) {
@@ -587,14 +469,9 @@ class Gen {
         // length are loaded while packet j runs (they travel with packet j's first loads), which
         // takes one dependent HBM round trip off every packet after the first.
         const bool pf = ctx == CTX_XDP && prefetch;
-        skb_touch = ctx == CTX_SKB && skb_lds && !skb_walk && !skb_fast && skb_touch_knob != 0 && !spread_on;
-        if (skb_touch) {
-            E.line("  uint64_t noff_ = 0;   // the next packet's offset (skb_touch)");
-            E.line("  { const uint32_t n_ = pkt_index(kp, g, 0u, ex_begin, ex_count); if (n_ != NO_PKT) noff_ = *gp(kp.pkt_off + n_); }");
-        }
         if (!spec_use.empty() && !spread_on) analyze_xpf();
         // (LDS budget: 4 blocks of 256 lanes per CU with the window alone; no other LDS user)
-        lpf_on = pf && xpf.on && lpf_knob && !xpf_knob && !spread_on && !stage && !vc_lds && !lds_stack_on && !defer_mode &&
+        lpf_on = pf && xpf.on && lpf_knob && !xpf_knob && !spread_on && !vc_lds && !lds_stack_on && !defer_mode &&
                  !hash_combine && lpf_safe();
         if (!lpf_on && !xpf_knob) xpf.on = false;   // (the one-packet-ahead form only on request)
         if (spread_own) {
@@ -698,19 +575,14 @@ class Gen {
             E.line("    if (nidx2_ != NO_PKT) { noff2_ = *gp(kp.pkt_off + nidx2_); nlen2_ = *gp(kp.pkt_len + nidx2_); }");
         } else if (pf) {
             E.line("    const uint64_t poff_ = noff_; const uint32_t plen_ = nlen_;");
-            if (nt) E.line("    { const uint32_t n_ = pkt_next(kp, i, j + 1, ex_begin, ex_count); if (n_ != NO_PKT) { noff_ = ld_nt(kp.pkt_off + n_); nlen_ = ld_nt(kp.pkt_len + n_); } }");
-            else if (spread_own) {
+            if (spread_own) {
                 E.line("    if (j + 1u < oQ_) { const uint32_t n_ = OWN_IDX(j + 1u); if (n_ != NO_PKT) { noff_ = *gp(br_.pkt_off + n_); nlen_ = *gp(br_.pkt_len + n_); } }");
                 E.line("    else if (bt_ + 1u < nb_ && oi_ != NO_PKT) { const BatchRef nx_ = cget(kp.many, bt_ + 1u); noff_ = *gp(nx_.pkt_off + oi_); nlen_ = *gp(nx_.pkt_len + oi_); bpre_ = true; }");
             }
             else if (spread_on) E.line("    { const uint32_t n_ = i + 256u; if (n_ < bhi_) { noff_ = *gp(kp.pkt_off + n_); nlen_ = *gp(kp.pkt_len + n_); } }");
             else E.line("    { const uint32_t n_ = pkt_next(kp, i, j + 1, ex_begin, ex_count); if (n_ != NO_PKT) { noff_ = *gp(kp.pkt_off + n_); nlen_ = *gp(kp.pkt_len + n_); } }");
         }
-        if (memtime) E.line("    const uint32_t mt0_ = (uint32_t)__builtin_amdgcn_s_memrealtime();");
-        // fields used once per packet are read through an opaque copy of the parameter pointer:
-        // loaded where used instead of hoisted out of the packet loop into SGPRs
-        if (kq_mode == 1) E.line("    const KParams *kqp_ = kpp; asm volatile(\"\" : \"+s\"(kqp_)); const KParams &kq_ = *kqp_;");
-        else E.line("    const KParams &kq_ = kp;");
+        E.line("    const KParams &kq_ = kp;");   // the once-per-packet fields' name in the generated text
         if (spread_own) {   // the packet's vCPU and its row of the spread map (chunked: per packet)
             E.line("    { const uint32_t ol_ = kp.sched == SCHED_CHUNKED ? i / oP_ : olane_;");
             E.line("      srow_ = ol_ - blockIdx.x * oR_;");
@@ -723,42 +595,13 @@ class Gen {
             E.line("      srow_ = lam_ >= lam0_ ? lam_ - lam0_ : lam_ + kp.cpu_lanes - lam0_;");
             E.line("      sbase_ = SM_.backing_addr + (uint32_t)L.cpu * SM_.addr_period; }");
         }
-        // The lane's private-memory and LDS addresses are loop-invariant; hoisted out of the packet
-        // loop they would stay live (one VGPR pair per stack slot) through every packet.  An opaque
-        // per-iteration copy of the lane index keeps each address next to its use.
-        if (opaque_lane) {
-            E.line("    { uint32_t ln_ = g; asm volatile(\"\" : \"+v\"(ln_)); L.lane = ln_; }");
-            if (stage && fast_paths) E.line("    uint32_t tl_ = tl0_; asm volatile(\"\" : \"+v\"(tl_));");
-        } else if (stage && fast_paths) {
-            E.line("    const uint32_t tl_ = tl0_;");
-        }
         if (ctx == CTX_SKB) {
             // NewProcess + LinuxContextSKBuff.Load (context_sk_buff.go:42-107, skb.h)
             E.line("    uint64_t r1 = 0;");
-            if (skb_walk)   // the process's SkbRec built in this lane's LDS slot: every field access reads LDS
-                E.line("    const int ls_ = skb_load_walk(kp, L, i, r1, srec_ + %uu * threadIdx.x, swin_);", kSrecQ);
-            else if (skb_fast)   // derived here from the header bytes (exception frames: the prep's words), into the LDS slot
-                E.line("    const int ls_ = skb_load_fast(kp, L, i, r1, srec_ + %uu * threadIdx.x, *gp(kq_.pkt_off + i), *gp(kq_.pkt_len + i), *gp(kq_.skb_prefix + i));", kSrecQ);
-            else if (skb_touch) {
-                E.line("    const uint64_t poff_ = noff_;");
-                E.line("    { const uint32_t n_ = pkt_next(kp, i, j + 1, ex_begin, ex_count); if (n_ != NO_PKT) noff_ = *gp(kp.pkt_off + n_); }");
-                // two dwords: packet bytes 14 and 38 (the Ethernet / IP / transport headers span at most
-                // two 64-byte halves of a 128-byte line whatever the slot's alignment); consumed at the
-                // packet's end, so the wait for them is long past
-                if (skb_touch_knob == 1) {
-                    E.line("    const uint32_t th0_ = *gp((const uint32_t *)(kq_.pkt_data + poff_ + SKB_HEADROOM + 12u));");
-                    E.line("    const uint32_t th1_ = *gp((const uint32_t *)(kq_.pkt_data + poff_ + SKB_HEADROOM + 36u));");
-                }
-                E.line("    const int ls_ = skb_load_lds_po(kp, L, i, r1, srec_ + %uu * threadIdx.x, poff_);", kSrecQ);
-                // consumed where the record's own wait already covers them (issued before it)
-                if (skb_touch_knob == 1) E.line("    asm volatile(\"\" :: \"v\"(th0_), \"v\"(th1_));");
-            } else if (skb_lds)   // the process's SkbRec into this lane's LDS slot: every field access reads LDS
+            if (skb_lds)   // the process's SkbRec into this lane's LDS slot: every field access reads LDS
                 E.line("    const int ls_ = skb_load_lds(kp, L, i, r1, srec_ + %uu * threadIdx.x);", kSrecQ);
             else
                 E.line("    const int ls_ = skb_load(kp, L, i, r1);");
-            // the window starts at the packet (skb.data = packet memory + 32)
-            if (stage && fast_paths)
-                E.line("    const uint32_t W_ = ls_ ? 0u : win_stage(pwin_, tl_, L.pkt + SKB_HEADROOM, L.M - SKB_HEADROOM);");
         } else {
             // NewProcess + LinuxContextXDP.Load (vm.go:198-235, context_xdp_md.go:47-115)
             E.line("    const uint32_t H = kq_.headroom_arr ? ld_nt(kq_.headroom_arr + i) : kq_.headroom;");
@@ -769,9 +612,6 @@ class Gen {
             } else if (spread_own) {
                 E.line("    const uint32_t len = *gp(br_.pkt_len + i);");
                 E.line("    L.pkt = br_.pkt_data + *gp(br_.pkt_off + i);");
-            } else if (nt) {
-                E.line("    const uint32_t len = ld_nt(kq_.pkt_len + i);");
-                E.line("    L.pkt = kq_.pkt_data + ld_nt(kq_.pkt_off + i);");
             } else {
                 E.line("    const uint32_t len = *gp(kq_.pkt_len + i);");
                 E.line("    L.pkt = kq_.pkt_data + *gp(kq_.pkt_off + i);");
@@ -786,7 +626,6 @@ class Gen {
             E.line("    L.ingress = (uint32_t)(kq_.ingress_arr ? ld_nt(kq_.ingress_arr + i) : kq_.ingress);");
             E.line("    L.rxq = (uint32_t)(kq_.rxq_arr ? ld_nt(kq_.rxq_arr + i) : kq_.rxq);");
             E.line("    L.egress = (uint32_t)(kq_.egress_arr ? ld_nt(kq_.egress_arr + i) : kq_.egress);");
-            if (stage && fast_paths) E.line("    const uint32_t W_ = win_stage(pwin_, tl_, L.pkt, L.M);");
             E.line("    uint64_t r1 = P + L.M + 1;");
         }
         E.line("    SM0(L) = 0; SM1(L) = 0; L.xdp_dirty = 0; L.nframes = 0; L.tailcalls = 0; L.t_lo = 0; L.t_n = 0; L.t_ptr = nullptr;");
@@ -838,14 +677,10 @@ class Gen {
             E.line("    break;");
         }
         E.line("  L_term:");
-        if (kq_mode == 2)   // the result pointers are loaded here, once per packet, not held in SGPRs
-            E.line("    { const KParams *kqp_ = kpp; asm volatile(\"\" : \"+s\"(kqp_)); const KParams &kq_ = *kqp_;");
-        else
-            E.line("    {");
-        E.line("#ifndef MIMIC_MEAS_NORES");
+        E.line("    {");
         {   // the owned form's results go to the batch of this iteration (br_)
             const char *rb = spread_own ? "br_" : "kq_";
-            if (nt || ntres) {
+            if (ntres) {
                 E.line("    if (%s.r0) st_nt(%s.r0 + i, r0);", rb, rb);
                 E.line("    if (%s.status) st_nt(%s.status + i, (uint8_t)st_);", rb, rb);
             } else {
@@ -853,12 +688,9 @@ class Gen {
                 E.line("    if (%s.status) *gp(%s.status + i) = (uint8_t)st_;", rb, rb);
             }
             if (census) E.line("    if (%s.steps) st_nt(%s.steps + i, coldn_);   // census: slow-path calls, not steps", rb, rb);
-            else if (memtime) E.line("    if (%s.steps) st_nt(%s.steps + i, (uint32_t)__builtin_amdgcn_s_memrealtime());", rb, rb);
             else E.line("    if (%s.steps) st_nt(%s.steps + i, steps);", rb, rb);
-            if (memtime) E.line("    if (%s.err_pc) st_nt(%s.err_pc + i, (int32_t)mt0_);", rb, rb);
-            else E.line("    if (%s.err_pc) st_nt(%s.err_pc + i, epc_);", rb, rb);
+            E.line("    if (%s.err_pc) st_nt(%s.err_pc + i, epc_);", rb, rb);
         }
-        E.line("#endif");
         E.line("    }");
         if (proc) {   // Process.Run: the whole state (interp.hip step_save), the process done
             E.line("    if (kq_.step) { StepState *S_ = kq_.step;");
@@ -872,7 +704,6 @@ class Gen {
         if (vc_on) E.line("  VC_FLUSH();");
         if (spread_own) {
             // the block's rows into the map: plain read-modify-writes (the block owns these vCPUs)
-            E.line("#if !defined(MIMIC_MEAS_NOFLUSH)   // (measurement knob: no flush, counters wrong)");
             E.line("  __syncthreads();");
             E.line("  if (ofw_ && sacc_[threadIdx.x]) *ofd_ = ofv_ + sacc_[threadIdx.x];");
             E.line("  for (uint32_t w_ = threadIdx.x + 256u; w_ < oR_ * SPREAD_ROWW; w_ += 256u) {   // rows past 256 words");
@@ -882,11 +713,10 @@ class Gen {
             E.line("    GAS spread_t *d_ = (GAS spread_t *)(kp.arena + SM_.dev_off + (size_t)(kp.vcpu_begin + blockIdx.x * oR_ + r_) * SM_.dev_stride) + q_;");
             E.line("    *d_ += v_;");
             E.line("  }");
-            E.line("#endif");
         } else if (spread_on) {
             // the block's counters into the map: one agent-scope add per non-zero counter (a row's
             // counters are contiguous in the arena, so consecutive threads add consecutive words)
-            E.line("#if SPREAD_ROWS && !defined(MIMIC_MEAS_NOFLUSH)   // (measurement knob: no flush, counters wrong)");
+            E.line("#if SPREAD_ROWS");
             E.line("  __syncthreads();");
             // a table that covers every vCPU lane (V <= packets per block): the block writes it,
             // rotated to absolute lanes, into its slice of kp.spread_part with plain stores, and
@@ -930,7 +760,6 @@ class Gen {
     // packet-entry fast paths: the entry's address, the window's offset in packet memory, and
     // the byte order of scalar accesses (sk_buff packets are BigEndian PlainMemory)
     const char *pa() const { return ctx == CTX_SKB ? "L.pa" : "P"; }
-    uint32_t wb() const { return ctx == CTX_SKB ? SKB_HEADROOM_J : 0u; }
     std::string ord(const std::string &v, uint32_t n) const {
         return ctx == CTX_SKB && n > 1 ? "bswap_n(" + v + ", " + std::to_string(n) + "u)" : v;
     }
@@ -1259,7 +1088,7 @@ class Gen {
         return true;
     }
     void analyze_xpf() {
-        if (!(xpf_knob || lpf_knob) || ctx != CTX_XDP || !prefetch || !window || stage || !fast_paths) return;
+        if (!(xpf_knob || lpf_knob) || ctx != CTX_XDP || !prefetch || !window || !fast_paths) return;
         for (auto &p : P) {
             if (p.n == 0) continue;
             bool to0 = false;
@@ -1400,7 +1229,7 @@ class Gen {
     // assertion of this analysis.
     bool analyze_spread() {
         if (!spread_req || ctx != CTX_XDP || !fast_paths || !cold_inline || careful_copies || any_local || any_tail ||
-            stage || census || !inc_knob || live.empty())
+            census || !inc_knob || live.empty())
             return false;
         int64_t map = -1;
         uint32_t n = 0;
@@ -1558,7 +1387,7 @@ class Gen {
         }
         E.line("%sga_ = %s;   // early load for slot %u", pre, addr(insn_src(x), insn_off(x)).c_str(), j);
         E.line("%sif ((uint64_t)(uint32_t)(ga_ - P) + %uu <= L.M) sp%u_%u_ = (%s)%s(L.pkt + (uint32_t)(ga_ - P), %uu);", pre, n, p.id, j,
-               n == 8 ? "uint64_t" : "uint32_t", nt ? "ld_n_nt" : "ld_n", n);
+               n == 8 ? "uint64_t" : "uint32_t", "ld_n", n);
     }
     // Early loads from one base register that fall in a 32-byte span are made as one window of
     // 8-byte loads (fewer memory instructions per packet); the fields are cut out of the window
@@ -1602,7 +1431,7 @@ class Gen {
             }
             E.line("      if ((uint64_t)wo_ + %uu <= L.M) {", 8 * words);
             for (uint32_t q = 0; q < words; q++)
-                E.line("        const uint64_t w%u_ = %s(L.pkt + wo_ + %uu, 8u);", q, nt ? "ld_n_nt" : "ld_n", 8 * q);
+                E.line("        const uint64_t w%u_ = %s(L.pkt + wo_ + %uu, 8u);", q, "ld_n", 8 * q);
             cut("w");
             E.line("      } else {");
             for (uint32_t j : js) emit_spec_one(p, j, "        ");
@@ -1660,22 +1489,16 @@ class Gen {
         }
     }
 
-    // the branch prefix of a slow path: "else " (or an if's condition) gets [[unlikely]], so the
-    // compiler lays the slow path out after the hot code (branch weights) instead of between its blocks
-    std::string unl(const std::string &pre) const {
-        if (!hint_knob) return pre;
-        return pre.size() >= 5 && pre.compare(pre.size() - 5, 5, "else ") == 0 ? pre + "[[unlikely]] " : pre;
-    }
     // the slow path of slot i of the program being emitted: a call (COLD_CALL) or a deferral
     std::string cold(const std::string &call, uint32_t i) const {
         if (defer_mode) return defer_text(i);
         return "COLD_CALL(" + call + ", " + std::to_string(i) + ");";
     }
     std::string defer_text(uint32_t i) const {
-        const uint16_t m = defer_noregs == 1 || defer_noregs == 10 + (int)cur_prog ? 0 : live.at(cur_prog).at(i) | 1u | (1u << 10);
+        const uint16_t m = live.at(cur_prog).at(i) | 1u | (1u << 10);
         std::string t = "{ DeferRec *dr_ = kp.defer + g;";
         for (uint32_t r = 0; r < 11; r++)
-            if ((m >> r) & 1) t += " dr_->r[" + std::to_string(r) + "] = " + (defer_noregs == 2 && r ? "(uint32_t)" : "") + "r" + std::to_string(r) + ";";
+            if ((m >> r) & 1) t += " dr_->r[" + std::to_string(r) + "] = r" + std::to_string(r) + ";";
         return t + " DFR(" + std::to_string(i) + "u, " + std::to_string(cur_prog) + "u); }";
     }
     // Registers live into each slot (backward dataflow over every program; a tail call continues
@@ -1895,14 +1718,9 @@ class Gen {
             // sk_buff packets: the fast STORE covers the frame only -- a store into a head- or tailroom
             // takes the generic path, which marks the batch's rooms-clean word (runtime.h
             // skb_room_mark); the same test on the loads cost the cfg-5 chain 2 VGPRs, its second wave
-            if (stage) {
-                const std::string wo = "(uint32_t)(ga_ - " + std::string(pa()) + " - " + std::to_string(wb()) + "u)";
-                f.push_back({"(uint64_t)" + wo + " + " + N + " <= W_", ord("win_load(pwin_, tl_, " + wo + ", " + N + ")", n), ""});
-            }
             f.push_back({"(uint64_t)" + o + " + " + N + " <= L.M",
-                         ord(std::string(nt ? "ld_n_nt" : "ld_n") + "(L.pkt + " + o + ", " + N + ")", n),
-                         "{ PKT_ST(L.pkt + " + o + ", " + N + ", " + ord(v, n) + ");" +
-                             (stage ? " win_store_rel(pwin_, tl_, W_, " + o + ", " + std::to_string(wb()) + "u, " + N + ", " + ord(v, n) + ");" : "") + " }",
+                         ord("ld_n(L.pkt + " + o + ", " + N + ")", n),
+                         "{ PKT_ST(L.pkt + " + o + ", " + N + ", " + ord(v, n) + "); }",
                          ctx == CTX_SKB ? "(uint64_t)(uint32_t)(" + o + " - SKB_HEADROOM) + " + N + " <= (L.rec->len & ~SKB_LOAD_FAILED)" : ""});
             // the lane's cached per-CPU row (analyze_vc): every access inside the row while the
             // cache is valid is served here, so memory and registers never disagree
@@ -1995,7 +1813,7 @@ class Gen {
         }
         skb_ptr_fast(i, base, off, n, true, dst, pre);
         // generic GetEntry + Load (cold, out of line)
-        E.line("%s{ %s %s = sp_.v; }", unl(pre).c_str(), cold("cold_load(kp, sp_, ga_, " + std::to_string(n) + "u)", i).c_str(), dst.c_str());
+        E.line("%s{ %s %s = sp_.v; }", pre.c_str(), cold("cold_load(kp, sp_, ga_, " + std::to_string(n) + "u)", i).c_str(), dst.c_str());
     }
 
     void store(uint32_t i, uint32_t base, int32_t off, uint32_t n, const std::string &val, bool deferred = false) {
@@ -2004,7 +1822,7 @@ class Gen {
         if (!deferred && elided.count({cur_prog, i})) {   // the write happens in the lookup's cold path
             const auto f = fast_forms(base, n, val);
             E.line("    // %u: key store deferred into the lookup's cold path (analyze_elide)", i);
-            E.line("    if (!(%s)) %s{ %s%s }", (f.at(0).scond.empty() ? f.at(0).cond : f.at(0).scond).c_str(), hint_knob ? "[[unlikely]] " : "", base == 10 && !spec_use.empty() ? "spv_ = 0u; " : "",
+            E.line("    if (!(%s)) { %s%s }", (f.at(0).scond.empty() ? f.at(0).cond : f.at(0).scond).c_str(), base == 10 && !spec_use.empty() ? "spv_ = 0u; " : "",
                    cold("cold_store(kp, sp_, ga_, " + std::to_string(n) + "u, " + val + ")", i).c_str());
             return;
         }
@@ -2031,11 +1849,9 @@ class Gen {
         }
         skb_ptr_fast(i, base, off, n, false, val, pre);
         // generic GetEntry + Store (cold); the stack / xdp_md state it may change comes back
-        E.line("%s{ %s%s", unl(pre).c_str(), base == 10 && !spec_use.empty() ? "spv_ = 0u; " : "",
+        E.line("%s{ %s%s", pre.c_str(), base == 10 && !spec_use.empty() ? "spv_ = 0u; " : "",
                cold("cold_store(kp, sp_, ga_, " + std::to_string(n) + "u, " + val + ")", i).c_str());
-        if (stage)  // a store that reached the packet updates the window too
-            E.line("      if (sp_.po) win_store_rel(pwin_, tl_, W_, sp_.po - 1u, %uu, %uu, %s); }", wb(), n, ord(val, n).c_str());
-        else E.line("    }");
+        E.line("    }");
     }
 
     void insn(const ProgView &p, uint32_t i) {
@@ -2170,7 +1986,7 @@ class Gen {
                 } else {
                     E.line("      if (!(mh_ && lookup_fast(kp, L, mh_ - 1u, r1, r2, r0))) {");
                 }
-                E.line("      if (!(%s)) %s%s } }", hfast.c_str(), hint_knob ? "[[unlikely]] " : "", cold("cold_lookup(kp, sp_)", i).c_str());
+                E.line("      if (!(%s)) %s } }", hfast.c_str(), cold("cold_lookup(kp, sp_)", i).c_str());
             } else {
                 // R1 is not an LD_IMM64 of this block: the generic helper reads the key from the
                 // stack, so a key store that analyze_elide deferred (analyze_fwd pairs store and call
@@ -2257,11 +2073,7 @@ class Gen {
         std::string pre = "    ";
         if (ctx == CTX_SKB && fast_paths) {
             E.line("    if ((uint32_t)r6 - SK_ <= SKB_STRUCT_SIZE && (uint64_t)(uint32_t)(%uu + ga_) + %s <= L.M) {", SKB_HEADROOM_J, N.c_str());
-            if (stage)
-                E.line("      if ((uint64_t)ga_ + %s <= W_) r0 = %s; else r0 = %s;", N.c_str(),
-                       ord("win_load(pwin_, tl_, ga_, " + N + ")", n).c_str(),
-                       ord("ld_n(L.pkt + (uint32_t)(" + std::to_string(SKB_HEADROOM_J) + "u + ga_), " + N + ")", n).c_str());
-            else if (spec_use.count({cur_prog, i}))
+            if (spec_use.count({cur_prog, i}))
                 E.line("      r0 = spv_ ? %s : %s;", ord("sp" + std::to_string(cur_prog) + "_" + std::to_string(i) + "_", n).c_str(),
                        ord("ld_n(L.pkt + (uint32_t)(" + std::to_string(SKB_HEADROOM_J) + "u + ga_), " + N + ")", n).c_str());
             else
@@ -2430,9 +2242,6 @@ std::string mimic_jit_source(const std::vector<DProg> &progs, const std::vector<
         info->early_loads = g.has_early_loads();
         info->cold_inline = g.cold_inline;
         info->defer = g.defer_mode;
-        info->skb_walk = g.skb_walk;
-        info->skb_fast = g.skb_fast;
-        info->karg = g.karg != 0;
         info->spread = g.spread_on;
         info->spread_own = g.spread_own;
         info->hash_combine = g.hash_combine;
@@ -2488,11 +2297,10 @@ int mimic_jit_prebuild_source(const std::string &src, std::string *log) {
     return build_code(src, code, log);
 }
 
-int mimic_jit_launch(hipFunction_t fn, const JitInfo &info, const KParams *kp, const KParams *d_kp, hipStream_t st) {
+int mimic_jit_launch(hipFunction_t fn, const KParams *kp, hipStream_t st) {
     const uint32_t blocks = (kp->lanes + 255) / 256;
     if (blocks == 0) return 0;
-    const KParams *p = d_kp;
-    void *args[] = {info.karg ? (void *)kp : (void *)&p};   // by value (kernarg segment) or a device copy
+    void *args[] = {(void *)kp};   // by value: the kernarg segment
     return hipModuleLaunchKernel(fn, blocks, 1, 1, 256, 1, 1, 0, st, args, nullptr) == hipSuccess ? 0 : -1;
 }
 

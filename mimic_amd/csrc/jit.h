@@ -15,10 +15,7 @@ struct JitInfo {
     bool tail_calls;     // some program calls bpf_tail_call
     bool early_loads;    // the kernel issues packet loads early (analyze_spec)
     bool cold_inline;    // the slow paths are inlined (small kernel, 4-wave register budget)
-    bool karg;           // the kernel takes KParams by value (kernarg segment), not a device copy
     bool defer;          // slow paths are deferred to the interpreter's resume kernel (launch it after)
-    bool skb_walk;       // sk_buff kernel that builds its SkbRecs itself (prep: footprints only)
-    bool skb_fast;       // sk_buff kernel that derives the records of common frames itself (sparse prep)
     bool spread;         // a spread kernel (a vCPU's packets on many lanes; jit.cpp analyze_spread)
     bool spread_own;     // ... in its owned form: a block runs every packet of its vCPUs (SpreadReq::own)
     bool hash_combine;   // pop-only inline inserts through the block combiner (hashmap.h h_comb_reserve)
@@ -56,8 +53,8 @@ std::string mimic_jit_source(const std::vector<DProg> &progs, const std::vector<
 uint64_t mimic_jit_step_bound(const JitInfo &info, uint32_t max_tail_calls);
 // hipRTC compile for gfx950 + module load on the current device (cached per device and source)
 int mimic_jit_compile(int device, const std::string &src, hipFunction_t *fn, std::string *log);
-// d_kp: the launch parameters in device memory
-int mimic_jit_launch(hipFunction_t fn, const JitInfo &info, const KParams *kp, const KParams *d_kp, hipStream_t st);
+// launch with kp by value (the kernel's one argument, in the kernarg segment)
+int mimic_jit_launch(hipFunction_t fn, const KParams *kp, hipStream_t st);
 // hipRTC compile only, no device needed
 int mimic_jit_check_source(const std::string &src, std::string *log, size_t *code_size);
 // source -> gfx950 code object (through the MIMIC_JIT_CACHE directory when set), no device

@@ -249,11 +249,9 @@ struct KParams {
     struct DeferRec *defer;
     uint32_t *defer_any;
     uint32_t defer_epoch;
-    // sk_buff batches: 1 when the prep kernel wrote every packet's SkbRec; 0 when the JIT kernel
-    // builds them itself (skb_load_walk) -- then the interpreter builds the ones it needs; 2 when
-    // the prep wrote the derived words of the frames skb_fast rejects only (skb_prefix flag
-    // SKB_PFX_EXC, skb.h) and the JIT kernel derives the rest (skb_load_fast)
-    uint32_t skb_rec_built;
+    // (reserved: the by-value kernarg layout is part of every JIT kernel's code, so the fields
+    // after this word keep their offsets -- see the static_asserts after the struct)
+    uint32_t reserved0;
     // spread launches (jit.cpp analyze_spread): a vCPU's packets run on many lanes; a generic
     // access that reaches per-CPU map memory would break that mode's exactness and sets *spread_bad
     // (never cleared: the host reports it as an engine error).  nullptr in every other launch.
@@ -290,6 +288,10 @@ struct KParams {
     // store into a head- or tailroom sets it to 0
     uint32_t *skb_rooms_state;
 };
+// JIT kernels take KParams by value: its layout is part of their machine code
+static_assert(sizeof(KParams) == 968, "KParams: the kernarg layout of every JIT kernel");
+static_assert(__builtin_offsetof(KParams, reserved0) == 356 && __builtin_offsetof(KParams, spread_bad) == 360,
+              "KParams: the fields around the reserved word keep their offsets");
 
 // A process a JIT lane suspended at a slow path (defer mode): the registers the slot and its
 // successors can read, the slot (PC) and program, the steps before the slot, the process's

@@ -190,15 +190,6 @@ DEV void st_n(uint8_t *p, uint32_t n, uint64_t v) {
 // Streaming accesses (packet bytes, descriptors, per-packet results) are each touched by one
 // process: non-temporal loads / stores keep them from evicting the lane-resident lines (per-CPU
 // map values, stack words) that later packets of the same vCPU reuse from L2.
-DEV uint64_t ld_n_nt(const uint8_t *p, uint32_t n) {
-    switch (n) {
-    case 1: return __builtin_nontemporal_load(gp(p));
-    case 2: return __builtin_nontemporal_load((const GAS u16u *)p);
-    case 4: return __builtin_nontemporal_load((const GAS u32u *)p);
-    case 8: return __builtin_nontemporal_load((const GAS u64u *)p);
-    default: return ld_n(p, n);
-    }
-}
 template <typename T>
 DEV T ld_nt(const T *p) { return __builtin_nontemporal_load(gp(p)); }
 template <typename T>
@@ -1006,54 +997,24 @@ DEV void skb_rooms_zero(uint8_t *pkt, uint32_t lw) {
 }
 // the rooms flag of a record the prep kernel built (skb.h SKB_DIRTY_Q)
 DEV bool skb_rec_dirty(const SkbRec &r) { return r.ip[0].pad[0] != 0; }
-DEV void skb_rooms_clear(uint8_t *pkt, uint32_t lw) {
-#if defined(MIMIC_ROOMS_MODE) && MIMIC_ROOMS_MODE == 2   // measurement only (MIMIC_JIT_ROOMS=2): rooms untouched
-    return;
-#endif
-    typedef uint64_t u64x2u __attribute__((ext_vector_type(2), aligned(1)));
-    const GAS u64x2u *h = (const GAS u64x2u *)pkt, *t = (const GAS u64x2u *)(pkt + SKB_HEADROOM + lw);
-    const u64x2u h0 = h[0], h1 = h[1], t0 = t[0], t1 = t[1], t2 = t[2], t3 = t[3];
-    const u64x2u o = h0 | h1 | t0 | t1 | t2 | t3;
-#if defined(MIMIC_ROOMS_MODE) && MIMIC_ROOMS_MODE == 0   // MIMIC_JIT_ROOMS=0: always written (round 2)
-    if (true) {
-#else
-    if (o.x | o.y) {
-#endif
-        const u64x2u z = {0, 0};
-        GAS u64x2u *hw = (GAS u64x2u *)pkt, *tw = (GAS u64x2u *)(pkt + SKB_HEADROOM + lw);
-        hw[0] = z;
-        hw[1] = z;
-        for (uint32_t q = 0; q < SKB_TAILROOM / 16; q++) tw[q] = z;
-    }
-}
-static_assert(SKB_HEADROOM == 32 && SKB_TAILROOM == 64, "skb_rooms_clear covers 2 + 4 16-byte chunks");
+static_assert(SKB_HEADROOM == 32 && SKB_TAILROOM == 64, "skb_rooms_zero covers 2 + 4 16-byte chunks");
 
-// NewProcess + LinuxContextSKBuff.Load (context_sk_buff.go:42-107) for packet i: the entries
-// of the skb.h layout, zeroed headroom / tailroom, R1 = the sk_buff address.  Returns 0 or
-// MIMIC_ERR_CTX_LOAD (SKBuffFromBytes failed, or AddEntry ran out of 32-bit address space;
-// then the packet memory is left untouched, as the reference never writes it).  When the batch's
-// records were not built by the prep kernel (KParams::skb_rec_built == 0: its JIT kernel builds
-// them in LDS) the record is built here first, unless `attach_only` (a process the resume kernel
-// re-attaches: its record, rooms and packet are what the JIT lane left).
 // packet i's leak prefix: within its prep block + the block's offset (skb.hip)
 // (the word's top bits are the prep kernel's flags, skb.h SKB_PFX_*)
 DEV uint64_t skb_leak_pre(const KParams &kp, uint32_t i) {
     return (kp.skb_prefix[i] & SKB_PFX_MASK) + kp.skb_prefix[kp.n + (i >> SKB_PREP_LOG2)];
 }
-// DECODE = false: a kernel only ever launched after a full prep (skb_rec_built == 1: the batch
-// interpreter and the Step kernel, engine.cpp run_xdp_impl) leaves SKBuffFromBytes out -- inlined it
-// is the largest register peak of the interpreter body (22 of its spilled VGPRs)
-template <bool DECODE = true>
+// NewProcess + LinuxContextSKBuff.Load (context_sk_buff.go:42-107) for packet i: the entries
+// of the skb.h layout, zeroed headroom / tailroom, R1 = the sk_buff address.  Returns 0 or
+// MIMIC_ERR_CTX_LOAD (SKBuffFromBytes failed, or AddEntry ran out of 32-bit address space;
+// then the packet memory is left untouched, as the reference never writes it).  The prep kernel
+// (skb.hip) built every packet's derived words and looked at its rooms.  `attach_only`: a process
+// the resume kernel re-attaches -- its record, rooms and packet are what the JIT lane left.
 DEV int skb_load(const KParams &kp, Lane &L, uint32_t i, uint64_t &r1, bool attach_only = false) {
     SkbRec *rec = kp.skb_rec + i;
     L.pkt = kp.pkt_data + kp.pkt_off[i];
-    const uint64_t pf = kp.skb_rec_built ? kp.skb_prefix[i] : 0ull;
-    // a sparse prep (skb_rec_built == 2) left derived words for the frames skb_fast rejects only:
-    // the others are decoded here from the packet bytes (the same record)
-    if ((!kp.skb_rec_built || (kp.skb_rec_built == 2 && !(pf & SKB_PFX_EXC))) && !attach_only) {
-        if (!DECODE) return MIMIC_ERR_ENGINE_HELPER;   // not launched so (engine invariant); loud if it were
-        skb_init(SkbBytes{L.pkt + SKB_HEADROOM}, kp.pkt_len[i], *rec);
-    } else if (kp.skb_drv && !attach_only)   // the prep kernel's derived words into the record
+    const uint64_t pf = kp.skb_prefix[i];
+    if (kp.skb_drv && !attach_only)   // the prep kernel's derived words into the record
         for (uint32_t q = 0; q < SKB_DERIVED_Q; q++) ((uint64_t *)rec)[q] = kp.skb_drv[(size_t)i * SKB_DERIVED_Q + q];
     const uint32_t lw = rec->len;
     L.rec = nullptr;
@@ -1071,17 +1032,14 @@ DEV int skb_load(const KParams &kp, Lane &L, uint32_t i, uint64_t &r1, bool atta
     L.ka = (uint32_t)ka;
     L.pa = L.ka + SKB_SK_SIZE + 1 + SKB_FK_SIZE + 1;
     L.M = SKB_HEADROOM + lw + SKB_TAILROOM;
-    if (!attach_only) {
-        if (!kp.skb_rec_built) skb_rooms_clear(L.pkt, lw);
-        else if (pf & SKB_PFX_DIRTY) skb_rooms_zero(L.pkt, lw);
-    }
+    if (!attach_only && (pf & SKB_PFX_DIRTY)) skb_rooms_zero(L.pkt, lw);
     r1 = kp.static_next + kp.stack_size + 1;
     return 0;
 }
 
 // skb_load's tail once the record of packet i is in place (LDS slot d): a user-given sock / flow
 // keys, entries, rooms, R1
-// dirty: the record's rooms flag (1 / 0), or -1 when no prep kernel looked (read the rooms here)
+// dirty: the record's rooms flag (1 / 0: the prep kernel looked)
 DEV int skb_attach(const KParams &kp, Lane &L, uint32_t i, uint64_t &r1, uint64_t *d, uint32_t lw, uint64_t pre, uint64_t base,
                    int dirty) {
     skb_apply_custom(*(SkbRec *)d, (const mimic_skb_custom *)kp.skb_custom, i);
@@ -1096,8 +1054,7 @@ DEV int skb_attach(const KParams &kp, Lane &L, uint32_t i, uint64_t &r1, uint64_
     L.ka = (uint32_t)ka;
     L.pa = L.ka + SKB_SK_SIZE + 1 + SKB_FK_SIZE + 1;
     L.M = SKB_HEADROOM + lw + SKB_TAILROOM;
-    if (dirty < 0) skb_rooms_clear(L.pkt, lw);
-    else if (dirty) skb_rooms_zero(L.pkt, lw);
+    if (dirty) skb_rooms_zero(L.pkt, lw);
     r1 = kp.static_next + kp.stack_size + 1;
     return 0;
 }
@@ -1105,12 +1062,8 @@ DEV int skb_attach(const KParams &kp, Lane &L, uint32_t i, uint64_t &r1, uint64_
 // skb_load for a JIT kernel that keeps the process's SkbRec in an LDS slot `d`: the record's words,
 // the packet offset and the leak prefix are loaded together (one memory round trip, not the
 // record length first and the rest after it), then the record goes to LDS.
-DEV int skb_load_lds_po(const KParams &kp, Lane &L, uint32_t i, uint64_t &r1, uint64_t *d, uint64_t po);
 DEV int skb_load_lds(const KParams &kp, Lane &L, uint32_t i, uint64_t &r1, uint64_t *d) {
-    return skb_load_lds_po(kp, L, i, r1, d, kp.pkt_off[i]);
-}
-// the same with packet i's offset given (loaded ahead by the caller)
-DEV int skb_load_lds_po(const KParams &kp, Lane &L, uint32_t i, uint64_t &r1, uint64_t *d, uint64_t po) {
+    const uint64_t po = kp.pkt_off[i];
     // the packet's derived words: 96 contiguous bytes of the prep kernel's compact array (consecutive
     // lanes, consecutive records), six 16-byte loads
     typedef uint64_t u64x2a __attribute__((ext_vector_type(2)));
@@ -1128,71 +1081,7 @@ DEV int skb_load_lds_po(const KParams &kp, Lane &L, uint32_t i, uint64_t &r1, ui
 #pragma unroll
     for (uint32_t q = 0; q < 8; q++) d[SKB_DERIVED_Q + q] = skb_writable_word(q);
     L.pkt = kp.pkt_data + po;
-#ifdef MIMIC_SKB_ROOMS_CHAIN   // measurement: the rooms read here (engine.cpp skb_prepare)
-    return skb_attach(kp, L, i, r1, d, (uint32_t)w[0], pre, base, -1);
-#else
     return skb_attach(kp, L, i, r1, d, (uint32_t)w[0], pre, base, (int)((w[SKB_DIRTY_Q] >> SKB_DIRTY_SHIFT) & 1u));
-#endif
-}
-
-// skb_load for a JIT kernel after a sparse prep (skb_rec_built == 2): the record of a common frame is
-// derived here, from the packet's first SKB_WIN bytes, straight into the LDS slot `d` (skb_fast_rec);
-// only a frame skb_fast does not take has its derived words in skb_drv (SKB_PFX_EXC).  The prep's
-// 96-byte record per packet is neither written nor read back: the header bytes this loads are the
-// ones the programs' early loads fetch next.  po / len: packet i's descriptor, pw: its prefix word
-// (the caller may have loaded them ahead).
-DEV int skb_load_fast(const KParams &kp, Lane &L, uint32_t i, uint64_t &r1, uint64_t *d, uint64_t po, uint32_t len,
-                      uint64_t pw) {
-    const uint64_t pre = (pw & SKB_PFX_MASK) + kp.skb_prefix[kp.n + (i >> SKB_PREP_LOG2)], base = *kp.skb_base;
-    L.pkt = kp.pkt_data + po;
-    typedef uint32_t u32x4u __attribute__((ext_vector_type(4), aligned(1)));   // any pkt_off
-    const GAS u32x4u *pk = (const GAS u32x4u *)(L.pkt + SKB_HEADROOM);
-    uint32_t w[SKB_WIN / 4];
-#pragma unroll
-    for (uint32_t c = 0; c < SKB_WIN / 16; c++) {   // chunks that start inside the packet
-        u32x4u v = {0u, 0u, 0u, 0u};
-        if (16 * c < len) v = pk[c];
-        w[4 * c] = v.x;
-        w[4 * c + 1] = v.y;
-        w[4 * c + 2] = v.z;
-        w[4 * c + 3] = v.w;
-    }
-    uint32_t lw;
-    if (pw & SKB_PFX_EXC) {
-        typedef uint64_t u64x2a __attribute__((ext_vector_type(2)));
-        const GAS u64x2a *s = (const GAS u64x2a *)(kp.skb_drv + (size_t)i * SKB_DERIVED_Q);
-        lw = (uint32_t)s[0].x;
-#pragma unroll
-        for (uint32_t q = 0; q < SKB_DERIVED_Q / 2; q++) {
-            const u64x2a v = s[q];
-            d[2 * q] = v.x;
-            d[2 * q + 1] = v.y;
-        }
-    } else {
-        SkbRec r;
-        skb_fast_rec(w, len, r);
-        const uint64_t *rw = (const uint64_t *)&r;
-#pragma unroll
-        for (uint32_t q = 0; q < SKB_DERIVED_Q; q++) d[q] = rw[q];
-        lw = len;
-    }
-#pragma unroll
-    for (uint32_t q = 0; q < 8; q++) d[SKB_DERIVED_Q + q] = skb_writable_word(q);
-    return skb_attach(kp, L, i, r1, d, lw, pre, base, (pw & SKB_PFX_DIRTY) ? 1 : 0);
-}
-
-// skb_load for a JIT kernel that builds the record itself (no prep records: a 160-byte write and
-// read per packet less): SKBuffFromBytes over the packet's first bytes staged in the block's LDS
-// windows (`win`, SkbWinBytes), straight into the LDS slot `d`
-DEV int skb_load_walk(const KParams &kp, Lane &L, uint32_t i, uint64_t &r1, uint64_t *d, uint32_t *win) {
-    const uint64_t po = kp.pkt_off[i], pre = skb_leak_pre(kp, i), base = *kp.skb_base;
-    const uint32_t len = kp.pkt_len[i];
-    L.pkt = kp.pkt_data + po;
-    const uint8_t *pkt = L.pkt + SKB_HEADROOM;
-    skb_stage<256u>(win, threadIdx.x, pkt, len);
-    SkbRec &r = *(SkbRec *)d;
-    skb_init(SkbWinBytes<256u>{win, pkt, threadIdx.x}, len, r);
-    return skb_attach(kp, L, i, r1, d, r.len, pre, base, -1);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1542,50 +1431,3 @@ DEV uint64_t alu32(uint32_t hi, uint64_t d, uint64_t x) {
     }
 }
 
-
-// ---------------------------------------------------------------------------------------
-// JIT packet window: the first bytes of each lane's packet memory staged in LDS, qword-
-// interleaved across the block's lanes ([q][lane]: uniform offsets are conflict-free).  The
-// window is a copy of global packet memory: every packet store updates both.
-// ---------------------------------------------------------------------------------------
-#define PWIN_Q 8u        // qwords per lane (64 bytes)
-#define PWIN_LANES 256u  // block size
-typedef uint64_t PWin[PWIN_Q][PWIN_LANES];
-
-// stage pkt[0, W) with W = min(M, 64) rounded down to whole qwords; returns W
-DEV uint32_t win_stage(PWin &w, uint32_t tl, const uint8_t *pkt, uint32_t M) {
-    const uint32_t W = M >= PWIN_Q * 8 ? PWIN_Q * 8 : (M & ~7u);
-#pragma unroll
-    for (uint32_t q = 0; q < PWIN_Q; q++)
-        if (q * 8 < W) w[q][tl] = *(const GAS u64u *)(pkt + q * 8);
-    return W;
-}
-// n bytes at offset o, o + n <= W
-DEV uint64_t win_load(const PWin &w, uint32_t tl, uint32_t o, uint32_t n) {
-    const uint32_t q = o >> 3, sh = (o & 7) * 8;
-    uint64_t v = w[q][tl] >> sh;
-    if (sh + 8 * n > 64) v |= w[q + 1][tl] << (64 - sh);
-    return n >= 8 ? v : (v & ((1ull << (8 * n)) - 1));
-}
-// mirror a packet store of n bytes at offset o (o < W) into the window
-DEV void win_store(PWin &w, uint32_t tl, uint32_t W, uint32_t o, uint32_t n, uint64_t v) {
-    const uint64_t m = n >= 8 ? ~0ull : ((1ull << (8 * n)) - 1);
-    v &= m;
-    const uint32_t q = o >> 3, sh = (o & 7) * 8;
-    w[q][tl] = (w[q][tl] & ~(m << sh)) | (v << sh);
-    if (sh + 8 * n > 64 && (q + 1) * 8 < W) {
-        const uint32_t bits = sh + 8 * n - 64;
-        const uint64_t m1 = (1ull << bits) - 1;
-        w[q + 1][tl] = (w[q + 1][tl] & ~m1) | (v >> (64 - sh));
-    }
-}
-// mirror a packet store of n bytes at packet-memory offset o into a window that covers packet
-// memory [wb, wb + W): the part of the store that overlaps the window, if any
-DEV void win_store_rel(PWin &w, uint32_t tl, uint32_t W, uint32_t o, uint32_t wb, uint32_t n, uint64_t v) {
-    if (o >= wb) {
-        if (o - wb < W) win_store(w, tl, W, o - wb, n, v);
-    } else if (o + n > wb && W > 0) {
-        const uint32_t d = wb - o;
-        win_store(w, tl, W, 0, n - d, v >> (8 * d));
-    }
-}

@@ -41,9 +41,7 @@
 #define SKB_SNAP 40u
 #define SKB_REC_BYTES 160u
 // flags in packet i's within-block leak prefix word (skb.hip; skb_leak_pre masks them off):
-//   EXC   the frame is one skb_fast does not take; with a sparse prep (KParams::skb_rec_built == 2)
-//         only such frames have their derived words in skb_drv, every other frame's record is built
-//         by whoever loads the process, from the packet's first bytes (skb_fast_rec);
+//   EXC   the frame is one skb_fast does not take: the general walk decoded it;
 //   DIRTY the packet memory's headroom or tailroom holds a non-zero byte (Load zeroes them)
 #define SKB_PFX_EXC (1ull << 63)
 #define SKB_PFX_DIRTY (1ull << 62)

@@ -24,8 +24,7 @@
 #define PREP_T 256u
 
 // packet i: packet bytes at pkt_data + pkt_off[i] + 32, pkt_len[i] of them; its derived record words
-// at rec + i * rec_q.  rec == nullptr: the
-// leak prefixes only (a JIT kernel that walks the headers itself builds the records in LDS).  Only
+// at rec + i * rec_q.  rec == nullptr: the leak prefixes only (tools/prep_probe.py).  Only
 // the records' derived words are written (skb.h SKB_DERIVED_Q: the writable state is constant at
 // Load and set by whoever loads the process).  They leave through LDS: each thread puts its
 // words there and the block writes them with consecutive threads on consecutive 8-byte words --
@@ -69,7 +68,6 @@ extern "C" __global__ __launch_bounds__(PREP_T) void mimic_skb_prep_kernel(uint8
                                                                           const uint32_t *__restrict__ pkt_len,
                                                                           uint32_t n, uint64_t *__restrict__ rec,
                                                                           uint32_t rec_q, uint64_t *__restrict__ prefix,
-                                                                          uint32_t rooms, uint32_t sparse,
                                                                           const uint32_t *__restrict__ rooms_state) {
     __shared__ uint64_t area[(PREP_W / 8) * PREP_T];   // the windows first, then the records
     __shared__ uint64_t wtot[PREP_T / 64];
@@ -78,8 +76,8 @@ extern "C" __global__ __launch_bounds__(PREP_T) void mimic_skb_prep_kernel(uint8
     if (i0 >= n) return;   // whole block past the batch (uniform: the barriers below are safe)
     const bool live = i < n;
     // the batch's rooms-clean word (mimic_skb_batch.rooms_state): 1 = an earlier launch left every
-    // room zero and no program store has touched one since -- nothing to read (rooms 3)
-    if (rooms == 1 && rooms_state && *rooms_state == 1u) rooms = 3;
+    // room zero and no program store has touched one since -- nothing to read
+    const bool clean = rooms_state && *rooms_state == 1u;
     SkbRec r;
     uint64_t f = 0;   // the leak footprint
     uint64_t flags = 0;   // skb.h SKB_PFX_*
@@ -98,20 +96,16 @@ extern "C" __global__ __launch_bounds__(PREP_T) void mimic_skb_prep_kernel(uint8
 #pragma unroll
         for (uint32_t c = 0; c < SKB_WIN / 16; c++) v[c] = *(const u32x4u *)(pkt + (16 * c < L ? 16 * c : 0u));
         // the rooms flag (skb.h SKB_DIRTY_Q): any non-zero byte in the 32 bytes before the packet
-        // or the 64 after it (rooms = 0: a measurement build whose JIT kernel reads them itself).
+        // or the 64 after it.
         // Loaded with the window, before the decode: one memory round trip per packet, not two
         // (the headroom shares the window's first line; the tailroom is the packet's last line).
         // Issued after the window and OR-ed after the decode: loads complete in order, so the
         // decode waits for the window only and runs while the tail line is still on its way
         // (measured: the rooms read cost 28 of the prep's 93 us when it was consumed first).
-#ifdef MIMIC_PREP_NOROOMS   // measurement only (tools/prep_probe.py): the rooms not read (flag always clean)
-        rooms = 0;
-#endif
-        // (rooms 0 / 1: loaded whatever `rooms` says, one straight-line load sequence for the wait
-        // counter; rooms 2: not read, zeroed below; rooms 3: known zero, not read)
+        // (a clean batch: known zero, not read)
         const u32x4u *hr = (const u32x4u *)(pkt - SKB_HEADROOM), *tr = (const u32x4u *)(pkt + L);
         u32x4u rh0 = {0, 0, 0, 0}, rh1 = rh0, rt[SKB_TAILROOM / 16];
-        if (rooms < 2) {
+        if (!clean) {
             rh0 = hr[0];
             rh1 = hr[1];
 #pragma unroll
@@ -138,35 +132,16 @@ extern "C" __global__ __launch_bounds__(PREP_T) void mimic_skb_prep_kernel(uint8
         u32x4u o = rh0 | rh1;
 #pragma unroll
         for (uint32_t c = 0; c < SKB_TAILROOM / 16; c++) o |= rt[c];
-        const uint32_t dirty = rooms == 1 && (o.x | o.y | o.z | o.w) ? 1u : 0u;
-        if (rooms == 2 && !(r.len & SKB_LOAD_FAILED)) {   // Load's zeroed rooms, written without a look
-            typedef uint32_t u32x4w __attribute__((ext_vector_type(4), aligned(1)));
-            const u32x4w z = {0, 0, 0, 0};
-            u32x4w *hw = (u32x4w *)(pkt - SKB_HEADROOM), *tw = (u32x4w *)(pkt + L);
-            hw[0] = z;
-            hw[1] = z;
-#pragma unroll
-            for (uint32_t c = 0; c < SKB_TAILROOM / 16; c++) tw[c] = z;
-        }
+#ifdef MIMIC_PREP_NOROOMS   // measurement only (tools/prep_probe.py): the rooms' flag always clean
+        const uint32_t dirty = 0u;
+#else
+        const uint32_t dirty = !clean && (o.x | o.y | o.z | o.w) ? 1u : 0u;
+#endif
         r.ip[0].pad[0] = dirty;
         f = (r.len & SKB_LOAD_FAILED) ? 0ull : (uint64_t)SKB_FOOT_FIXED + L;
         flags = (dirty ? SKB_PFX_DIRTY : 0ull) | (fast ? 0ull : SKB_PFX_EXC);
     }
-    if (rec && sparse) {
-        // sparse: only the frames skb_fast does not take leave their derived words (the loader builds
-        // every other record itself from the packet's first bytes, skb.h skb_fast_rec): few threads
-        // store, each its own 96 bytes
-        if (live && (flags & SKB_PFX_EXC)) {
-            typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
-            const uint64_t *rw = (const uint64_t *)&r;
-            u64x2 *o = (u64x2 *)(rec + (size_t)i * rec_q);
-#pragma unroll
-            for (uint32_t u = 0; u < SKB_DERIVED_Q / 2; u++) {
-                const u64x2 v = {rw[2 * u], rw[2 * u + 1]};
-                o[u] = v;
-            }
-        }
-    } else if (rec) {
+    if (rec) {
 #ifdef MIMIC_PREP_DIRECT   // measurement: each thread writes its own derived words (16-byte stores)
         if (live) {
             typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
@@ -287,23 +262,21 @@ extern "C" __global__ __launch_bounds__(BLK_T) void mimic_skb_blocks_kernel(uint
 extern "C" int mimic_skb_prep_only(const uint8_t *pkt_data, const uint64_t *pkt_off, const uint32_t *pkt_len, uint32_t n,
                                    uint64_t *rec, uint32_t rec_q, uint64_t *prefix, uint64_t *state, hipStream_t st) {
     hipLaunchKernelGGL(mimic_skb_prep_kernel, dim3((n + PREP_T - 1) / PREP_T), dim3(PREP_T), 0, st, (uint8_t *)pkt_data, pkt_off, pkt_len, n,
-                       rec, rec_q, prefix, 1u, 0u, (const uint32_t *)nullptr);
+                       rec, rec_q, prefix, (const uint32_t *)nullptr);
     hipLaunchKernelGGL(mimic_skb_blocks_kernel, dim3(1), dim3(BLK_T), 0, st, prefix + n, (n + PREP_T - 1) / PREP_T, state,
                        0ull, 0u, (uint32_t *)nullptr);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-// prefix: n + ceil(n / 256) words; state: 2 words.  sparse: derived words for the frames skb_fast
-// does not take only (SKB_PFX_EXC), every packet's flags in its prefix word
+// prefix: n + ceil(n / 256) words (every packet's flags in its word); state: 2 words
 extern "C" int mimic_launch_skb_prep(const uint8_t *pkt_data, const uint64_t *pkt_off, const uint32_t *pkt_len,
                                      uint32_t n, uint64_t *rec, uint32_t rec_q, uint64_t *prefix, uint64_t *state,
-                                     uint64_t init_base, uint32_t use_init, uint32_t rooms, uint32_t sparse,
-                                     uint32_t *rooms_state, hipStream_t st) {
+                                     uint64_t init_base, uint32_t use_init, uint32_t *rooms_state, hipStream_t st) {
     if (n)
         hipLaunchKernelGGL(mimic_skb_prep_kernel, dim3((n + PREP_T - 1) / PREP_T), dim3(PREP_T), 0, st, (uint8_t *)pkt_data, pkt_off, pkt_len, n,
-                           rec, rec_q, prefix, rooms, sparse, (const uint32_t *)rooms_state);
+                           rec, rec_q, prefix, (const uint32_t *)rooms_state);
     hipLaunchKernelGGL(mimic_skb_blocks_kernel, dim3(1), dim3(BLK_T), 0, st, prefix + n, (n + PREP_T - 1) / PREP_T, state,
-                       init_base, use_init, rooms == 1 ? rooms_state : (uint32_t *)nullptr);
+                       init_base, use_init, rooms_state);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -31,18 +31,19 @@ def _progs_args(raws: Sequence[bytes]):
 
 
 def kernel_source(raws: Sequence[bytes], ctx: int = CTX_XDP, vc: Sequence[Tuple[int, int, int]] = (), spread=None,
-                  proc: bool = False) -> str:
+                  proc: bool = False, no_early_loads: bool = False) -> str:
     """vc: (program index, slot, E * S) of the LD_IMM64 slots that name a per-CPU array whose
     per-vCPU row is at most 128 bytes, a multiple of 8 -- what a VM with those maps generates (see
     ``vc_slots``).  spread: a ``spread_spec`` -- the VM's spread kernel instead (xdp_md).  proc: the
-    single-process form Process.Run tiers up to (MIMIC_PROC_JIT, xdp_md)."""
+    single-process form Process.Run tiers up to (MIMIC_PROC_JIT, xdp_md).  no_early_loads: the form
+    the engine falls back to when the kernel's 4-wave build spills (engine.cpp)."""
     if spread is not None:
         return spread_source(raws, *spread)[0]
     lib = _lib.load()
     keep, arr, ns = _progs_args(raws)
     flat = [v for t in vc for v in t]
     vca = (C.c_uint32 * max(len(flat), 1))(*flat)
-    kind = ctx | (0x100 if proc else 0)
+    kind = ctx | (0x100 if proc else 0) | (0x200 if no_early_loads else 0)
     n = lib.mimic_jit_source_vc(arr, ns, len(raws), kind, vca, len(vc), None, 0)
     if n < 0:
         raise ValueError(f"cannot decode programs ({n})")
@@ -183,20 +184,6 @@ def _cache_dir() -> str:
     return d
 
 
-def _no_early_load_source(k) -> str:
-    """The form of kernel k the engine falls back to when its 4-wave build spills (engine.cpp:
-    the kernel without early packet loads, MIMIC_JIT_SPEC=0)."""
-    old = os.environ.get("MIMIC_JIT_SPEC")
-    os.environ["MIMIC_JIT_SPEC"] = "0"
-    try:
-        return kernel_source(list(k[0]), *k[1:])
-    finally:
-        if old is None:
-            del os.environ["MIMIC_JIT_SPEC"]
-        else:
-            os.environ["MIMIC_JIT_SPEC"] = old
-
-
 def prewarm(kernels: Iterable[Tuple], workers: int = 0) -> Dict[str, float]:
     """Compile the kernels of (raws, ctx[, vc]) program sets into MIMIC_JIT_CACHE using `workers`
     parallel processes (0: min(16, cpus) - 1), then, for those whose 4-wave build spills, the
@@ -215,7 +202,7 @@ def prewarm(kernels: Iterable[Tuple], workers: int = 0) -> Dict[str, float]:
         if "issued early" in src and "amdgpu_waves_per_eu(4)" in src:
             try:
                 if kernel_resources(code_object(src))["scratch"] > 0:
-                    alt[_no_early_load_source(k)] = None
+                    alt[kernel_source(list(k[0]), *k[1:], no_early_loads=True)] = None
             except RuntimeError:
                 pass
     info2 = _compile_parallel(list(alt), workers)

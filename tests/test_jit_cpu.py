@@ -130,7 +130,7 @@ def test_hot_kernels_register_budget(fn, vgprs, waves):
     """cfg 2 / cfg 3 kernels as the bench's VM generates them (the classifier with its lane value
     cache): unified VGPRs within budget, no VGPR spills, no scratch.  A few SGPRs may spill (into
     VGPR lanes): keeping the per-packet result pointers in SGPRs measured faster than reloading
-    them (jit.cpp, MIMIC_JIT_KQ); the generic lookup's fallback to h_find for keys over 32 bytes
+    them (44.6 vs 52-54 us per cfg-2 launch); the generic lookup's fallback to h_find for keys over 32 bytes
     (hashmap.h h_find_ro, inlined into every kernel's cold lookup) costs the classifier 8 more.  parse5's early packet loads (jit.cpp, analyze_spec)
     cost it the fifth wave and measured faster anyway: 1.155 vs 1.193 ms per launch; forcing 5
     waves (MIMIC_JIT_WAVES=5) measured 1.47 ms.  The classifier's deferred key store
