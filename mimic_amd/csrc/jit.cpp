@@ -405,9 +405,35 @@ class Gen {
             E.line("#define OWN_IDX_C(k_) ((threadIdx.x + 256u * (k_) < oR_ * oP_ && (uint64_t)blockIdx.x * oR_ * oP_ + threadIdx.x + 256u * (k_) < kp.n) ? (uint32_t)((uint64_t)blockIdx.x * oR_ * oP_ + threadIdx.x + 256u * (k_)) : NO_PKT)");
             E.line("#define OWN_IDX(k_) (kp.sched == SCHED_CHUNKED ? OWN_IDX_C(k_) : OWN_IDX_I(k_))");
             E.line("  const uint32_t oi_ = OWN_IDX(0u);");
+            // (OWN_IDX is used for the thread's first packet only, oi_.)  What is uniform for the launch
+            // is read from the kernarg segment once.  A thread's next packet is its index + ostr_
+            // while that is below olim_: interleaved, the stride oS_ * cpu_lanes under n (a stride past 2^32
+            // saturates: index + 0xffffffff is never below n); chunked, 256 under the end of the
+            // block's packets -- OWN_IDX(k + 1) given that OWN_IDX(k) is a packet.
+            E.line("  const bool ochk_ = kp.sched == SCHED_CHUNKED;");
+            E.line("  const uint64_t ostr64_ = ochk_ ? 256ull : (uint64_t)oS_ * kp.cpu_lanes;");
+            E.line("  const uint64_t oend_ = (uint64_t)blockIdx.x * oR_ * oP_ + (uint32_t)(oR_ * oP_);");
+            // ofl_: the launch has per-packet context arrays (1) or rooms (2); a plain launch with no
+            // rooms (0) reads no room and no array per packet.
+            E.line("  uint32_t ofl_ = __builtin_amdgcn_readfirstlane((kp.headroom_arr || kp.tailroom_arr || kp.ingress_arr || kp.rxq_arr || kp.egress_arr ? 1u : 0u) | (kp.headroom | kp.tailroom ? 2u : 0u));");
+            E.line("  uint32_t ocpu_ = kp.vcpu_begin + olane_, oep_ = kp.entry_prog, or10_ = kp.static_next + kp.frame_size;");
+            // (pinned: the compiler would otherwise sink these loads back to their uses in the loop)
+            E.line("  uint32_t ostr_ = ostr64_ < 0xffffffffull ? (uint32_t)ostr64_ : 0xffffffffu;");
+            E.line("  uint32_t olim_ = ochk_ && oend_ < kp.n ? (uint32_t)oend_ : kp.n;");
+            E.line("  asm volatile(\"\" : \"+s\"(ostr_), \"+s\"(olim_), \"+s\"(ofl_), \"+s\"(oep_), \"+s\"(or10_));");
+            E.line("  asm volatile(\"\" : \"+v\"(ocpu_));");
+            E.line("  uint32_t oin_ = (uint32_t)kp.ingress, orx_ = (uint32_t)kp.rxq, oeg_ = (uint32_t)kp.egress;");
+            E.line("  asm volatile(\"\" : \"+s\"(oin_), \"+s\"(orx_), \"+s\"(oeg_));");
+            E.line("%s", kOwnHoist);   // the instruction-table words the programs use (own_hoist)
             E.line("  const DMap SM_ = cget(kp.maps, SPREAD_MAP);");
             E.line("  __shared__ spread_t sacc_[SPREAD_ROWS * SPREAD_ROWW];");
             E.line("  for (uint32_t w_ = threadIdx.x; w_ < SPREAD_ROWS * SPREAD_ROWW; w_ += 256u) sacc_[w_] = 0;");
+            // The launch's batch references in LDS (512 bytes): the result arrays' addresses, and the
+            // next batch's descriptor arrays at a batch boundary, are read from here where they are
+            // used -- the r0 / status / steps / err_pc pointers and their null tests then hold no SGPR
+            // across the packet loop, where SGPRs are what runs out
+            E.line("  __shared__ BatchRef obr_[MIMIC_MANY_MAX];");
+            E.line("  if (threadIdx.x < (kp.many_n ? kp.many_n : 1u)) obr_[threadIdx.x] = kp.many_n ? cget(kp.many, threadIdx.x) : BatchRef{kp.pkt_data, kp.pkt_off, kp.pkt_len, kp.r0, kp.status, kp.steps, kp.err_pc, 0};");
             E.line("  __syncthreads();");
             E.line("  uint32_t srow_ = orow_, sbase_ = 0;");
             // the row words this thread adds into at the end, loaded now (their round trip overlaps
@@ -479,7 +505,10 @@ class Gen {
             // of batch 1, ... (all batches have the same n, so the same packet indices), the block's
             // LDS counter table accumulating over all of them and flushed once; the last packet of a
             // batch prefetches the next batch's first descriptor.  many_n = 0: the one batch in kp.
-            if (pf) E.line("  uint64_t noff_ = 0; uint32_t nlen_ = 0;");
+            // The descriptor of the running packet lives in poff_ / plen_ across iterations: the
+            // prefetched one (noff_ / nlen_) is moved there at the end of the packet before, ahead of
+            // its result stores, so the next packet's first loads wait for nothing.
+            if (pf) E.line("  uint64_t noff_ = 0, poff_ = 0; uint32_t nlen_ = 0, plen_ = 0;");
             E.line("  const uint32_t nb_ = kp.many_n ? kp.many_n : 1u;");
             E.line("  bool bpre_ = false;   // this batch's first descriptor came with the previous batch's last packet");
             E.line("  for (uint32_t bt_ = 0; bt_ < nb_; bt_++) {");
@@ -528,7 +557,7 @@ class Gen {
             E.line("  if (nidx2_ != NO_PKT) { noff2_ = *gp(kp.pkt_off + nidx2_); nlen2_ = *gp(kp.pkt_len + nidx2_); }");
         } else if (pf) {
             if (spread_own)
-                E.line("  if (!bpre_ && oi_ != NO_PKT) { noff_ = *gp(br_.pkt_off + oi_); nlen_ = *gp(br_.pkt_len + oi_); } bpre_ = false;");
+                E.line("  if (!bpre_ && oi_ != NO_PKT) { poff_ = *gp(br_.pkt_off + oi_); plen_ = *gp(br_.pkt_len + oi_); } bpre_ = false;");
             else
                 E.line("  uint64_t noff_ = 0; uint32_t nlen_ = 0;");
             if (spread_own) {
@@ -538,9 +567,12 @@ class Gen {
                 E.line("  { const uint32_t n_ = pkt_index(kp, g, 0u, ex_begin, ex_count); if (n_ != NO_PKT) { noff_ = *gp(kp.pkt_off + n_); nlen_ = *gp(kp.pkt_len + n_); } }");
         }
         if (spread_own) {
+            E.line("  uint32_t oni_ = oi_;   // the thread's next packet");
             E.line("  for (uint32_t j = 0; j < oQ_; j++) {   // the thread's packets of its lane, in order");
-            E.line("    const uint32_t i = j ? OWN_IDX(j) : oi_;");
+            E.line("    const uint32_t i = oni_;");
             E.line("    if (i == NO_PKT) break;");
+            E.line("    oni_ = NO_PKT;");
+            E.line("    if (j + 1u < oQ_) { const uint64_t x_ = (uint64_t)i + ostr_; if (x_ < olim_) oni_ = (uint32_t)x_; }");
         } else if (spread_on) {
             E.line("  for (uint32_t j = 0; j < SPREAD_PPB / 256u; j++) {");
             E.line("    const uint32_t i = blo_ + j * 256u + threadIdx.x;");
@@ -574,19 +606,19 @@ class Gen {
             E.line("    nidx2_ = nidx_ != NO_PKT ? pkt_next(kp, nidx_, j + 2u, ex_begin, ex_count) : NO_PKT;");
             E.line("    if (nidx2_ != NO_PKT) { noff2_ = *gp(kp.pkt_off + nidx2_); nlen2_ = *gp(kp.pkt_len + nidx2_); }");
         } else if (pf) {
-            E.line("    const uint64_t poff_ = noff_; const uint32_t plen_ = nlen_;");
+            if (!spread_own) E.line("    const uint64_t poff_ = noff_; const uint32_t plen_ = nlen_;");
             if (spread_own) {
-                E.line("    if (j + 1u < oQ_) { const uint32_t n_ = OWN_IDX(j + 1u); if (n_ != NO_PKT) { noff_ = *gp(br_.pkt_off + n_); nlen_ = *gp(br_.pkt_len + n_); } }");
-                E.line("    else if (bt_ + 1u < nb_ && oi_ != NO_PKT) { const BatchRef nx_ = cget(kp.many, bt_ + 1u); noff_ = *gp(nx_.pkt_off + oi_); nlen_ = *gp(nx_.pkt_len + oi_); bpre_ = true; }");
+                E.line("    if (j + 1u < oQ_) { if (oni_ != NO_PKT) { noff_ = *gp(br_.pkt_off + oni_); nlen_ = *gp(br_.pkt_len + oni_); } }");
+                E.line("    else if (bt_ + 1u < nb_ && oi_ != NO_PKT) { const BatchRef &nx_ = obr_[bt_ + 1u]; noff_ = *gp(nx_.pkt_off + oi_); nlen_ = *gp(nx_.pkt_len + oi_); bpre_ = true; }");
             }
             else if (spread_on) E.line("    { const uint32_t n_ = i + 256u; if (n_ < bhi_) { noff_ = *gp(kp.pkt_off + n_); nlen_ = *gp(kp.pkt_len + n_); } }");
             else E.line("    { const uint32_t n_ = pkt_next(kp, i, j + 1, ex_begin, ex_count); if (n_ != NO_PKT) { noff_ = *gp(kp.pkt_off + n_); nlen_ = *gp(kp.pkt_len + n_); } }");
         }
         E.line("    const KParams &kq_ = kp;");   // the once-per-packet fields' name in the generated text
         if (spread_own) {   // the packet's vCPU and its row of the spread map (chunked: per packet)
-            E.line("    { const uint32_t ol_ = kp.sched == SCHED_CHUNKED ? i / oP_ : olane_;");
+            E.line("    { const uint32_t ol_ = ochk_ ? i / oP_ : olane_;");
             E.line("      srow_ = ol_ - blockIdx.x * oR_;");
-            E.line("      L.cpu = (int32_t)(kp.vcpu_begin + ol_);");
+            E.line("      L.cpu = (int32_t)(ocpu_ - olane_ + ol_);");
             E.line("      sbase_ = SM_.backing_addr + (uint32_t)L.cpu * SM_.addr_period; }");
         } else if (spread_on) {   // this packet's vCPU (the schedule's lane for it) and its row of the spread map
             E.line("    { if (kp.sched == SCHED_CHUNKED) lam_ = i / kp.per_lane;");
@@ -604,8 +636,20 @@ class Gen {
                 E.line("    const int ls_ = skb_load(kp, L, i, r1);");
         } else {
             // NewProcess + LinuxContextXDP.Load (vm.go:198-235, context_xdp_md.go:47-115)
+            if (spread_own) {   // a plain launch (ofl_ = 0): no room, no array; only the interface scalars
+                E.line("    uint32_t H = 0u, T = 0u;");
+                E.line("    L.ingress = oin_; L.rxq = orx_; L.egress = oeg_;");
+                E.line("    if (ofl_) {");
+                E.line("      H = kq_.headroom_arr ? ld_nt(kq_.headroom_arr + i) : kq_.headroom;");
+                E.line("      T = kq_.tailroom_arr ? ld_nt(kq_.tailroom_arr + i) : kq_.tailroom;");
+                E.line("      if (kq_.ingress_arr) L.ingress = (uint32_t)ld_nt(kq_.ingress_arr + i);");
+                E.line("      if (kq_.rxq_arr) L.rxq = (uint32_t)ld_nt(kq_.rxq_arr + i);");
+                E.line("      if (kq_.egress_arr) L.egress = (uint32_t)ld_nt(kq_.egress_arr + i);");
+                E.line("    }");
+            } else {
             E.line("    const uint32_t H = kq_.headroom_arr ? ld_nt(kq_.headroom_arr + i) : kq_.headroom;");
             E.line("    const uint32_t T = kq_.tailroom_arr ? ld_nt(kq_.tailroom_arr + i) : kq_.tailroom;");
+            }
             if (pf) {
                 E.line("    const uint32_t len = plen_;");
                 E.line("    L.pkt = %s + poff_;", spread_own ? "br_.pkt_data" : "kq_.pkt_data");
@@ -619,18 +663,25 @@ class Gen {
             E.line("    L.M = H + len + T;");
             E.line("    L.pa = P;");
             E.line("    L.rec = nullptr;");
+            if (spread_own) E.line("    if (ofl_) {");   // (no rooms to zero in a plain launch)
             E.line("    for (uint32_t b = 0; b < H; b++) *gp(L.pkt + b) = 0;");
             E.line("    for (uint32_t b = 0; b < T; b++) *gp(L.pkt + H + len + b) = 0;");
+            if (spread_own) E.line("    }");
             E.line("    L.data = P + H;");
             E.line("    L.data_end = P + H + len;");
+            if (!spread_own) {
             E.line("    L.ingress = (uint32_t)(kq_.ingress_arr ? ld_nt(kq_.ingress_arr + i) : kq_.ingress);");
             E.line("    L.rxq = (uint32_t)(kq_.rxq_arr ? ld_nt(kq_.rxq_arr + i) : kq_.rxq);");
             E.line("    L.egress = (uint32_t)(kq_.egress_arr ? ld_nt(kq_.egress_arr + i) : kq_.egress);");
+            }
             E.line("    uint64_t r1 = P + L.M + 1;");
         }
         E.line("    SM0(L) = 0; SM1(L) = 0; L.xdp_dirty = 0; L.nframes = 0; L.tailcalls = 0; L.t_lo = 0; L.t_n = 0; L.t_ptr = nullptr;");
         E.line("    uint64_t r0 = 0, r2 = 0, r3 = 0, r4 = 0, r5 = 0, r6 = 0, r7 = 0, r8 = 0, r9 = 0;");
-        E.line("    uint64_t r10 = kp.static_next + kp.frame_size;");
+        // (the owned form's copy is pinned again per packet: the stack arithmetic of the cold paths
+        // would otherwise be hoisted out of the loop, one live SGPR per derived value)
+        if (spread_own) E.line("    uint32_t lr10_ = or10_; asm volatile(\"\" : \"+s\"(lr10_));");
+        E.line("    uint64_t r10 = %s;", spread_own ? "lr10_" : "kp.static_next + kp.frame_size");
         E.line("    uint32_t steps = 0;");
         if (census) E.line("    coldn_ = 0;");
         if (!spec_use.empty()) E.line("    spv_ = 1;");
@@ -645,7 +696,7 @@ class Gen {
         if (dispatch_on()) {
             // one dispatch block for the entry and every tail call (see dispatch_on)
             E.line("    uint32_t cur_;   // no initializer: the TERM gotos above jump past it");
-            E.line("    cur_ = kp.entry_prog;");
+            E.line("    cur_ = %s;", spread_own ? "oep_" : "kp.entry_prog");
             E.line("    switch (cur_) {");
             for (auto &p : P)
                 if (p.n == 0) E.line("    case %u: steps = 1; TERM(MIMIC_ERR_PC_OOB, 0);", p.id);  // vm.go:297-299
@@ -660,7 +711,7 @@ class Gen {
             E.line("    default: TERM(MIMIC_ERR_ENGINE_HELPER, -1);");
             E.line("    }");
         } else {
-            E.line("    switch (kp.entry_prog) {");
+            E.line("    switch (%s) {", spread_own ? "oep_" : "kp.entry_prog");
             for (auto &p : P) {
                 if (p.n == 0) E.line("    case %u: steps = 1; TERM(MIMIC_ERR_PC_OOB, 0);", p.id);  // vm.go:297-299
                 else E.line("    case %u: goto P%u_0;", p.id, p.id);
@@ -677,9 +728,16 @@ class Gen {
             E.line("    break;");
         }
         E.line("  L_term:");
+        // the owned form takes the next packet's descriptor here, ahead of the result stores: the
+        // wait for it (it came back with this packet's first loads) is the last one before the next
+        // packet's window loads, which the stores' acknowledgements then travel with
+        if (spread_own && pf) E.line("    poff_ = noff_; plen_ = nlen_; asm volatile(\"\" : \"+v\"(poff_), \"+v\"(plen_));");
         E.line("    {");
-        {   // the owned form's results go to the batch of this iteration (br_)
-            const char *rb = spread_own ? "br_" : "kq_";
+        {   // the owned form's results go to the batch of this iteration, its addresses read from the
+            // block's LDS copy of the batch references (obr_): no SGPR holds them across the loop
+            const char *rb = spread_own ? "lb_" : "kq_";
+            // (by reference: each address is read just ahead of its store)
+            if (spread_own) E.line("    const BatchRef &lb_ = obr_[bt_];");
             if (ntres) {
                 E.line("    if (%s.r0) st_nt(%s.r0 + i, r0);", rb, rb);
                 E.line("    if (%s.status) st_nt(%s.status + i, (uint8_t)st_);", rb, rb);
@@ -743,6 +801,24 @@ class Gen {
         E.line("  if (kp.lane_steps) st_nt(kp.lane_steps + g, lane_steps);");
         if (hash_chunk) E.line("  h_chunk_fini();   // the block's last wave hands its chunk's remainder back");
         E.line("}");
+        if (spread_own) {
+            // own_hoist: the instruction-table words the emitted programs use (an LD_IMM64 slot's
+            // constant, own_k; its map hint, own_h -- only the half that is used), read once ahead of
+            // the batch loop and pinned in SGPRs
+            std::string hs;
+            char b[512];
+            for (uint32_t s : own_k) {
+                snprintf(b, sizeof b, "  uint64_t hk%u_ = cget(kp.insns, %uu).k; asm volatile(\"\" : \"+s\"(hk%u_));\n", s, s, s);
+                hs += b;
+            }
+            for (uint32_t s : own_h) {
+                snprintf(b, sizeof b, "  uint32_t hh%u_ = AUX_MAPHINT(cget(kp.insns, %uu).aux); asm volatile(\"\" : \"+s\"(hh%u_));\n", s, s, s);
+                hs += b;
+            }
+            if (!hs.empty()) hs.pop_back();
+            const size_t q = E.s.find(kOwnHoist);
+            E.s.replace(q, strlen(kOwnHoist), hs);
+        }
         if (census) {   // diagnostics: each slow-path call adds 1 to its kind's 4-bit field of coldn_
             static const char *kinds[] = {"cold_load(", "cold_store(", "cold_lookup(", "cold_update(", "cold_delete(",
                                           "cold_tailcall(", "cold_ldabs(", "cold_adjust_tail("};
@@ -765,6 +841,10 @@ class Gen {
     }
     static constexpr uint32_t SKB_HEADROOM_J = 32;
     bool any_tail = false, any_local = false, all_leaders = false;
+    // owned form: slots whose instruction-table constant (own_k) or map hint (own_h) the kernel
+    // reads once per launch; their declarations replace kOwnHoist when the programs are out
+    static constexpr const char *kOwnHoist = "  //@own_hoist@";
+    std::set<uint32_t> own_k, own_h;
     uint32_t blk_start = 0;   // first slot of the basic block being emitted
     uint32_t cur_prog = 0;    // program being emitted
 
@@ -1874,7 +1954,8 @@ class Gen {
                    reg(d).c_str(), xop(x).c_str());
             break;
         case H_LDIMM:  // read from the table: map relocations do not change the kernel source
-            E.line("    %s = cget(kp.insns, %uu).k;", reg(d).c_str(), p.base + i);
+            if (spread_own) { own_k.insert(p.base + i); E.line("    %s = hk%u_;", reg(d).c_str(), p.base + i); }
+            else E.line("    %s = cget(kp.insns, %uu).k;", reg(d).c_str(), p.base + i);
             break;
         case H_JA:
             E.s += "    ";
@@ -1972,7 +2053,11 @@ class Gen {
         case 1: {
             const int64_t j = fast_paths ? r1_def(p, i) : -1;
             if (j >= 0) {  // inline array lookup when R1 is the map object the LD_IMM64 hint names
-                E.line("    { const uint32_t mh_ = AUX_MAPHINT(cget(kp.insns, %uu).aux);", p.base + (uint32_t)j);
+                // (the owned form read the hint once per launch: own_hoist; the in-loop pin keeps
+                // what derives from it out of the loop's live SGPRs)
+                const uint32_t hs = p.base + (uint32_t)j;
+                if (spread_own) { own_h.insert(hs); E.line("    { uint32_t mh_ = hh%u_; asm volatile(\"\" : \"+s\"(mh_));", hs); }
+                else E.line("    { const uint32_t mh_ = AUX_MAPHINT(cget(kp.insns, %uu).aux);", hs);
                 auto f = fwd_call.find({p.id, i});
                 // array maps inline (with the key forwarded from its stack store when known); then
                 // hash maps inline (the key read from the stack); then the generic helper
