@@ -31,6 +31,7 @@ DIV0, SHIFT, BADREG, CALLX, PANIC_PC, HELPER_NEG, STEP_LIMIT, CALL_DEPTH, ENGINE
     16, 17, 18, 19, 20, 21, 22, 23, 24)
 
 CASES = []
+JIT_GROUP = 0   # cases added later carry a higher number: kat.jit_groups chunks them after all earlier chunks
 
 
 def case(name, items, expect, ref, packet=b"\x00" * 64, vcpus=1, maps=(), map_init=(), prog_array=(),
@@ -45,7 +46,7 @@ def case(name, items, expect, ref, packet=b"\x00" * 64, vcpus=1, maps=(), map_in
                       maps=list(maps), map_init=[[m, k.hex(), v.hex(), c] for m, k, v, c in map_init],
                       prog_array=list(prog_array), cpu=cpu, headroom=headroom, tailroom=tailroom,
                       ingress=ingress, rxq=rxq, egress=egress, step_budget=step_budget,
-                      max_tail_calls=max_tail_calls, expect=expect))
+                      max_tail_calls=max_tail_calls, expect=expect, **({"jit_group": JIT_GROUP} if JIT_GROUP else {})))
 
 
 def e(r0=None, status=OK, steps=None, err_pc=-1):
@@ -474,6 +475,54 @@ case("percpu_hash_object_not_vmmem", [A.ld_map_fd(1, "ph"), A.ldx(4, 0, 1, 0), A
      "inst.go:308-311", vcpus=2, maps=[PH])
 straight("percpu_hash_e2big", h_upd(1, 1, "ph") + h_upd(2, 2, "ph") + h_upd(3, 3, "ph"), 7,
          "emulator_linux_map_hash.go:584-590", vcpus=2, maps=[PH])
+
+
+# ------------------------------------------------------------------------------------------
+# later additions: chunked after every case above (jit_group), so that the JIT chunks of the cases
+# above keep their programs, their kernels and their test ids
+# ------------------------------------------------------------------------------------------
+JIT_GROUP = 1
+# jge / jle / jsge in the three classes; each vector differs from the neighbouring reading
+# (the other width, the other signedness, or the strict comparison)
+jcase("jge_x_low32_equal", 0x1_0000_0005, 5, A.jmp("jge", 1, 2, 1, reg=True), True, "inst_gen.go:634 (Q1)")
+jcase("jge_x_low32_below", 0x1_0000_0000, 5, A.jmp("jge", 1, 2, 1, reg=True), False, "inst_gen.go:634 (Q1: 64-bit would be taken)")
+jcase("jle_x_low32_equal", 0x1_0000_0005, 5, A.jmp("jle", 1, 2, 1, reg=True), True, "inst_gen.go:679 (Q1: 64-bit would not be taken)")
+jcase("jle_x_low32_above", 6, 0x1_0000_0005, A.jmp("jle", 1, 2, 1, reg=True), False, "inst_gen.go:679 (Q1)")
+jcase("jsge_x_int32_min", 0x8000_0000, 1, A.jmp("jsge", 1, 2, 1, reg=True), False, "inst_gen.go:662 (Q1: int32 view)")
+jcase("jsge_x_int32_minus1", 1, 0xFFFF_FFFF, A.jmp("jsge", 1, 2, 1, reg=True), True, "inst_gen.go:662 (Q1: 1 >= -1)")
+jcase("jsge_x_int32_equal", 0xAAAA_0000_8000_0000, 0x8000_0000, A.jmp("jsge", 1, 2, 1, reg=True), True, "inst_gen.go:662 (Q1)")
+jcase("jge_k_equal_signext", M64, 0, A.jmp("jge", 1, -1, 1), True, "inst_gen.go:629 (uint64(Constant))")
+jcase("jge_k_unsigned", 5, 0, A.jmp("jge", 1, -1, 1), False, "inst_gen.go:629 (5 < 2^64-1)")
+jcase("jge_k_64", 0x1_0000_0000, 0, A.jmp("jge", 1, 5, 1), True, "inst_gen.go:629")
+jcase("jle_k_equal", 5, 0, A.jmp("jle", 1, 5, 1), True, "inst_gen.go:676")
+jcase("jle_k_64", 0x1_0000_0000, 0, A.jmp("jle", 1, 5, 1), False, "inst_gen.go:676")
+jcase("jle_k_unsigned", 5, 0, A.jmp("jle", 1, -1, 1), True, "inst_gen.go:676 (uint64(Constant))")
+jcase("jsge_k_equal", M64, 0, A.jmp("jsge", 1, -1, 1), True, "inst_gen.go:657")
+jcase("jsge_k_int64_min", 0x8000_0000_0000_0000, 0, A.jmp("jsge", 1, 0, 1), False, "inst_gen.go:657")
+jcase("jsge_k_64", 0x8000_0000, 0, A.jmp("jsge", 1, 1, 1), True, "inst_gen.go:657 (int64: 2^31 >= 1)")
+jcase("jge32_k_low32", 0x1_0000_0000, 0, A.jmp32("jge", 1, 1, 1), False, "inst_gen.go:630")
+jcase("jge32_k_equal", 0xFFFF_FFFF, 0, A.jmp32("jge", 1, -1, 1), True, "inst_gen.go:630 (uint32(Constant))")
+jcase("jle32_k_low32_equal", 0x1_0000_0005, 0, A.jmp32("jle", 1, 5, 1), True, "inst_gen.go:677")
+jcase("jle32_k_unsigned", 0xFFFF_FFFF, 0, A.jmp32("jle", 1, 1, 1), False, "inst_gen.go:677")
+jcase("jsge32_k_int32_min", 0x8000_0000, 0, A.jmp32("jsge", 1, 1, 1), False, "inst_gen.go:658 (int32 view)")
+jcase("jsge32_k_low32", 0x1_7FFF_FFFF, 0, A.jmp32("jsge", 1, -1, 1), True, "inst_gen.go:658")
+jcase("jsge32_k_equal", 0xFFFF_FFFF, 0, A.jmp32("jsge", 1, -1, 1), True, "inst_gen.go:658")
+
+
+# ARSH by a register at exactly the width and at 32 in the 64-bit form
+def arsh_x(name, is64, a, n, r, ref):
+    case(name, [A.ld_imm64(0, a), A.mov64_imm(2, n), (A.alu64 if is64 else A.alu32)("arsh", 0, 2, reg=True), A.exit_()],
+         e(r0=r, steps=5), ref)
+
+
+arsh_x("arsh64_x_32", True, 0x8000_0000_0000_0000, 32, 0xFFFFFFFF80000000, "inst.go:132-136")
+arsh_x("arsh64_x_64_negative", True, 0x8000_0000_0000_0000, 64, M64, "inst.go:132-136 (count == width: the sign fill)")
+arsh_x("arsh64_x_64_positive", True, 0x4000_0000_0000_0000, 64, 0, "inst.go:132-136")
+arsh_x("arsh32_x_32_negative", False, 0x8000_0000, 32, M64, "inst.go:121-125 (count == width, sign-extended)")
+arsh_x("arsh32_x_32_positive", False, 0x4000_0000, 32, 0, "inst.go:121-125")
+arsh_x("arsh32_x_64_negative", False, 0xFFFF_FFFF_8000_0000, 64, M64, "inst.go:121-125")
+arsh_x("arsh32_x_64_positive", False, 0xFFFF_FFFF_7FFF_FFFF, 64, 0, "inst.go:121-125 (int32(dst): the high word is dropped)")
+
 
 def main():
     out = os.path.join(HERE, "kat.json")

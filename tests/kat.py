@@ -42,12 +42,14 @@ def _setup_key(c):
 def jit_groups(cases, max_progs: int = 40):
     """Single-program KATs with the same VM setup (vCPUs, maps, MaxTailCalls, map init), chunked
     into VMs of up to max_progs programs: one JIT kernel runs a whole chunk, each case with its own
-    entry program.  Returns [(scenario, runs, cases)]; multi-program cases are left out."""
+    entry program.  Returns [(scenario, runs, cases)]; multi-program cases are left out.  Cases with
+    a "jit_group" (vectors added to the fixture later) are chunked after all the others, in the
+    order of that number, so the earlier chunks keep their programs and their test ids."""
     groups = {}
     for c in cases:
         if len(c["progs"]) != 1 or c["prog_array"]:
             continue
-        groups.setdefault(_setup_key(c), []).append(c)
+        groups.setdefault((c.get("jit_group", 0), _setup_key(c)), []).append(c)
     out = []
     for key in sorted(groups):
         cs = groups[key]
