@@ -35,7 +35,10 @@ extern "C" {
 #endif
 
 #define MIMIC_ABI_VERSION 4  /* 2: mimic_skb_batch.custom, statuses 29-30, MIMIC_EXEC_SPREAD; 3: MIMIC_EXEC_SPREAD_OWN;
-                                4: status 31, thread-safe process calls, mimic_run_xdp_many */
+                                4: status 31, thread-safe process calls, mimic_run_xdp_many.
+                                Still 4 although mimic_xdp_batch grew by pkt_stride / pkt_len_all (128 ->
+                                136 bytes): the number does NOT tell the two layouts apart; check
+                                mimic_xdp_batch_size() against sizeof(mimic_xdp_batch), see there */
 
 /* errors */
 #define MIMIC_EINVAL (-1)
@@ -127,10 +130,17 @@ typedef struct {
 } mimic_reloc;
 
 /* One batch of xdp_md processes.  All pointers are DEVICE pointers; NULL arrays fall
- * back to the scalar next to them.  Packet memory i is pkt_data[pkt_off[i] ..
+ * back to the scalar next to them (pkt_off and pkt_len: to the two scalars at the end).
+ * Packet memory i is pkt_data[pkt_off[i] ..
  * pkt_off[i]+H+L+T) with the packet at +H (context_xdp_md.go:52-64); the engine zeroes the
  * headroom/tailroom bytes, then runs the program on that memory IN PLACE, so the caller
- * sees every packet write afterwards. */
+ * sees every packet write afterwards.
+ * Uniform batches (a ring of fixed-size slots) need no per-packet descriptors: with pkt_off NULL
+ * packet memory i starts at pkt_data + (uint64_t)i * pkt_stride, with pkt_len NULL every packet
+ * is pkt_len_all bytes long.  The two are independent (fixed slots with varying lengths drop
+ * pkt_off only); the kernels then load no descriptor for the packet, 12 bytes per packet less.
+ * pkt_off NULL with pkt_stride 0 and n > 1 is MIMIC_EINVAL.  mimic_skb_batch,
+ * mimic_xdp_host_batch and the Go binding have no such form: they still need both arrays. */
 typedef struct {
     uint32_t n;
     uint32_t schedule;          /* MIMIC_SCHED_* */
@@ -144,6 +154,8 @@ typedef struct {
     const int32_t *egress_ifindex;  int32_t egress_all;
     const int32_t *cpu;         /* HOST array for MIMIC_SCHED_EXPLICIT (the engine builds the per-vCPU lists) */
     uint64_t step_budget;       /* 0 = MIMIC default; the per-process watchdog (contexts: mimic_run_xdp_ctx) */
+    uint32_t pkt_stride;        /* pkt_off == NULL: bytes from one packet memory to the next */
+    uint32_t pkt_len_all;       /* pkt_len == NULL: the length of every packet */
 } mimic_xdp_batch;
 
 typedef struct {                /* DEVICE arrays of n entries, any may be NULL */
@@ -154,6 +166,15 @@ typedef struct {                /* DEVICE arrays of n entries, any may be NULL *
 } mimic_xdp_results;
 
 int mimic_abi_version(void);
+/* sizeof(mimic_xdp_batch) in the library.  The struct grew by pkt_stride / pkt_len_all (128 -> 136
+ * bytes) without a new MIMIC_ABI_VERSION, so this is the check that tells the layouts apart.  A caller
+ * and a library that disagree are compatible only through the single-batch entry points
+ * (mimic_run_xdp, mimic_run_xdp_ctx) with both pkt_off and pkt_len given: the engine reads the two
+ * fields only when the array is NULL (a NULL pkt_off, EINVAL before, then reads 8 bytes past a
+ * 128-byte struct).  mimic_run_xdp_many walks an ARRAY of the struct: with the sizes different,
+ * batches 1.. are read at the wrong offsets and their pointers reach the device -- every caller of it
+ * must be built against this header and should refuse to run when this value is not its sizeof. */
+int mimic_xdp_batch_size(void);
 const char *mimic_last_error(const mimic_vm *vm);
 
 /* NewLinuxEmulator(OptMaxTailCalls) + NewVM(VMOptEmulator, VMOptSetvCPUs). vm.go:54-76 */
@@ -231,7 +252,8 @@ int mimic_stack_addr(mimic_vm *vm, uint32_t *addr_out);
 int mimic_run_xdp(mimic_vm *vm, uint32_t prog_id, const mimic_xdp_batch *batch,
                   const mimic_xdp_results *results, void *hip_stream);
 /* k batches (DEVICE pointers as above), enqueued like mimic_run_xdp, as few launches as possible: up
- * to 8 batches of the same size, schedule (not EXPLICIT) and scalar fields, with no per-packet arrays,
+ * to 8 batches of the same size, schedule (not EXPLICIT) and scalar fields, with no per-packet context
+ * arrays (each batch with or without pkt_off / pkt_len of its own, any pkt_stride / pkt_len_all),
  * run as ONE launch when the programs allow the owned spread kernel (mimic_set_spread); every vCPU
  * then runs its packets of batch 0, then of batch 1, ... (processPool draining a backlog of batches,
  * vm.go:548-573).  Otherwise one launch per batch.  Not in the reference API. */

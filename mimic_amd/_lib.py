@@ -59,7 +59,8 @@ class XDPBatch(C.Structure):
                 ("ingress_ifindex", C.c_void_p), ("ingress_all", C.c_int32),
                 ("rx_queue_index", C.c_void_p), ("rxq_all", C.c_int32),
                 ("egress_ifindex", C.c_void_p), ("egress_all", C.c_int32),
-                ("cpu", C.c_void_p), ("step_budget", C.c_uint64)]
+                ("cpu", C.c_void_p), ("step_budget", C.c_uint64),
+                ("pkt_stride", C.c_uint32), ("pkt_len_all", C.c_uint32)]
 
 
 class SKBBatch(C.Structure):
@@ -103,6 +104,7 @@ class XDPHostBatch(C.Structure):
 
 EXPORTS = {
     "mimic_abi_version": (C.c_int, []),
+    "mimic_xdp_batch_size": (C.c_int, []),
     "mimic_last_error": (C.c_char_p, [C.c_void_p]),
     "mimic_vm_create": (C.c_int, [C.POINTER(VMSettings), C.POINTER(C.c_void_p)]),
     "mimic_vm_destroy": (None, [C.c_void_p]),
@@ -205,5 +207,8 @@ def load() -> C.CDLL:
         fn.argtypes = args
     if lib.mimic_abi_version() != ABI_VERSION:
         raise ImportError("libmimic_amd.so ABI version mismatch")
+    # (the version did not move when mimic_xdp_batch grew: mimic_run_xdp_many walks an array of it)
+    if lib.mimic_xdp_batch_size() != C.sizeof(XDPBatch):
+        raise ImportError("libmimic_amd.so: sizeof(mimic_xdp_batch) differs from the binding's")
     _lib = lib
     return lib

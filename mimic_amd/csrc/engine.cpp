@@ -702,6 +702,7 @@ static int decode_program(const uint8_t *raw, uint32_t n_slots, std::vector<DIns
 extern "C" {
 
 int mimic_abi_version(void) { return MIMIC_ABI_VERSION; }
+int mimic_xdp_batch_size(void) { return (int)sizeof(mimic_xdp_batch); }
 
 const char *mimic_last_error(const mimic_vm *vm) { return vm ? vm->err.c_str() : "null vm"; }
 
@@ -1718,6 +1719,18 @@ static int run_xdp_impl(mimic_vm *vm, uint32_t prog_id, const mimic_xdp_batch *b
                         hipStream_t st_in, uint64_t shift, const SkbRun *skb = nullptr, const StepRun *step = nullptr,
                         const CtxRun *cx = nullptr, ManyRun *mr = nullptr);
 
+// What every xdp batch must carry, whichever launch runs it: packet memory, and a way to each packet
+// (pkt_off, or a stride; a null pkt_len needs nothing, its pkt_len_all may be any length).  `at` names
+// the batch of a mimic_run_xdp_many call (-1: the call's only batch).
+static int xdp_batch_check(mimic_vm *vm, const mimic_xdp_batch *b, int64_t at) {
+    const char *why = nullptr;
+    if (b->n > 0 && !b->pkt_data) why = "missing packet memory";
+    else if (b->n > 1 && !b->pkt_off && !b->pkt_stride) why = "no pkt_off and pkt_stride 0: every packet at the same address";
+    if (!why) return 0;
+    if (at < 0) return fail(vm, MIMIC_EINVAL, "%s", why);
+    return fail(vm, MIMIC_EINVAL, "batch %lld: %s", (long long)at, why);
+}
+
 int mimic_run_xdp(mimic_vm *vm, uint32_t prog_id, const mimic_xdp_batch *b, const mimic_xdp_results *res,
                   void *hip_stream) {
     return run_xdp_impl(vm, prog_id, b, res, (hipStream_t)hip_stream, 0);
@@ -1731,7 +1744,14 @@ int mimic_run_xdp_many(mimic_vm *vm, uint32_t prog_id, const mimic_xdp_batch *b,
                        void *hip_stream) {
     if (!vm || (k && (!b || !res))) return MIMIC_EINVAL;
     hipStream_t st = (hipStream_t)hip_stream;
-    // batches that can share a launch: same size, schedule and scalar fields, no per-packet arrays
+    // every batch of the call is checked before any of them runs: a launch that takes several reads
+    // batches 1.. from its BatchRefs, past run_xdp_impl's own check of the one it is given
+    if (k && prog_id >= vm->progs.size()) return fail(vm, MIMIC_EINVAL, "no program with id '%u' is loaded", prog_id);
+    for (uint32_t q = 0; q < k; q++)
+        if (const int rc = xdp_batch_check(vm, b + q, q)) return rc;
+    // batches that can share a launch: same size, schedule and scalar fields, no per-packet context
+    // arrays; pkt_off / pkt_len may be arrays in some and null (uniform) in others, each with its own
+    // stride and length
     auto same = [&](const mimic_xdp_batch &x, const mimic_xdp_batch &y) {
         return x.n == y.n && x.schedule == y.schedule && x.schedule != MIMIC_SCHED_EXPLICIT && !x.headroom && !y.headroom &&
                !x.tailroom && !y.tailroom && !x.ingress_ifindex && !y.ingress_ifindex && !x.rx_queue_index &&
@@ -2034,7 +2054,8 @@ static int run_xdp_impl(mimic_vm *vm, uint32_t prog_id, const mimic_xdp_batch *b
                         const CtxRun *cx, ManyRun *mr) {
     if (!vm || !b || !res) return MIMIC_EINVAL;
     if (prog_id >= vm->progs.size()) return fail(vm, MIMIC_EINVAL, "no program with id '%u' is loaded", prog_id);
-    if (b->n > 0 && (!b->pkt_data || !b->pkt_off || !b->pkt_len)) return fail(vm, MIMIC_EINVAL, "missing packet arrays");
+    if (const int brc = xdp_batch_check(vm, b, -1)) return brc;
+    if (skb && b->n > 0 && (!b->pkt_off || !b->pkt_len)) return fail(vm, MIMIC_EINVAL, "missing packet arrays");
     if (cx && cx->all && cx->per_packet) return fail(vm, MIMIC_EINVAL, "one context for the batch or one per packet, not both");
     if (cx && cx->all && !cx->all->pinned) return fail(vm, MIMIC_EDEVICE, "the context was made without a device");
     if (cx && cx->per_packet)
@@ -2118,6 +2139,8 @@ static int run_xdp_impl(mimic_vm *vm, uint32_t prog_id, const mimic_xdp_batch *b
     kp.pkt_data = b->pkt_data;
     kp.pkt_off = b->pkt_off;
     kp.pkt_len = b->pkt_len;
+    kp.pkt_stride = b->pkt_off ? 0u : b->pkt_stride;     // (read only when the array is null)
+    kp.pkt_len_all = b->pkt_len ? 0u : b->pkt_len_all;
     kp.headroom_arr = b->headroom;
     kp.tailroom_arr = b->tailroom;
     kp.ingress_arr = b->ingress_ifindex;
@@ -2434,9 +2457,12 @@ static int run_xdp_impl(mimic_vm *vm, uint32_t prog_id, const mimic_xdp_batch *b
         mr->used = jit && own && !ji.defer && mr->k >= 1 && mr->k <= MIMIC_MANY_MAX;
         if (mr->used) {
             kp.many_n = mr->k;
-            for (uint32_t q = 0; q < mr->k; q++)
-                kp.many[q] = BatchRef{mr->b[q].pkt_data, mr->b[q].pkt_off, mr->b[q].pkt_len, mr->r[q].r0, mr->r[q].status,
-                                      mr->r[q].steps, mr->r[q].err_pc, 0};
+            for (uint32_t q = 0; q < mr->k; q++) {
+                const mimic_xdp_batch &bq = mr->b[q];
+                kp.many[q] = BatchRef{bq.pkt_data, bq.pkt_off, bq.pkt_len, mr->r[q].r0, mr->r[q].status, mr->r[q].steps,
+                                      mr->r[q].err_pc,
+                                      (bq.pkt_off ? 0u : bq.pkt_stride) | (uint64_t)(bq.pkt_len ? 0u : bq.pkt_len_all) << 32};
+            }
         }
     }
     if (jit) {  // launch parameters by value: the runtime copies them into the kernarg segment

@@ -68,7 +68,10 @@ static __device__ __noinline__ void step_warm(const KParams &kp, uint32_t t, uin
         const uint64_t lines = (spans[k][1] + 63) / 64;
         for (uint64_t q = t; q < lines && q < 4096; q += nt) n += *(const volatile uint32_t *)(spans[k][0] + q * 64);
     }
-    if (t == 0) n += *(const volatile uint32_t *)kp.pkt_off + *(const volatile uint32_t *)kp.pkt_len;
+    if (t == 0) {   // (a uniform batch has no descriptor arrays to warm)
+        if (kp.pkt_off) n += *(const volatile uint32_t *)kp.pkt_off;
+        if (kp.pkt_len) n += *(const volatile uint32_t *)kp.pkt_len;
+    }
     (void)n;
 }
 #define NREGS 11
@@ -230,8 +233,8 @@ static __device__ __forceinline__ void xdp_body(const KParams *__restrict__ kpp,
         } else if (i != 0xffffffffu) {
             const uint32_t H = kp.headroom_arr ? kp.headroom_arr[i] : kp.headroom;
             const uint32_t T = kp.tailroom_arr ? kp.tailroom_arr[i] : kp.tailroom;
-            const uint32_t len = kp.pkt_len[i];
-            L.pkt = kp.pkt_data + kp.pkt_off[i];
+            const uint32_t len = pkt_len_at(kp, i);
+            L.pkt = kp.pkt_data + pkt_off_at(kp, i);
             L.M = H + len + T;
             if (!resume_here) {
                 for (uint32_t b = 0; b < H; b++) L.pkt[b] = 0;

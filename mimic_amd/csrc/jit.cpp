@@ -414,7 +414,8 @@ class Gen {
             E.line("  const uint64_t ostr64_ = ochk_ ? 256ull : (uint64_t)oS_ * kp.cpu_lanes;");
             E.line("  const uint64_t oend_ = (uint64_t)blockIdx.x * oR_ * oP_ + (uint32_t)(oR_ * oP_);");
             // ofl_: the launch has per-packet context arrays (1) or rooms (2); a plain launch with no
-            // rooms (0) reads no room and no array per packet.
+            // rooms (0) reads no room and no array per packet.  Bits 4 and 8, set per batch below: the
+            // batch has no pkt_off / no pkt_len (a uniform batch, runtime.h pkt_off_at).
             E.line("  uint32_t ofl_ = __builtin_amdgcn_readfirstlane((kp.headroom_arr || kp.tailroom_arr || kp.ingress_arr || kp.rxq_arr || kp.egress_arr ? 1u : 0u) | (kp.headroom | kp.tailroom ? 2u : 0u));");
             E.line("  uint32_t ocpu_ = kp.vcpu_begin + olane_, oep_ = kp.entry_prog, or10_ = kp.static_next + kp.frame_size;");
             // (pinned: the compiler would otherwise sink these loads back to their uses in the loop)
@@ -433,7 +434,7 @@ class Gen {
             // used -- the r0 / status / steps / err_pc pointers and their null tests then hold no SGPR
             // across the packet loop, where SGPRs are what runs out
             E.line("  __shared__ BatchRef obr_[MIMIC_MANY_MAX];");
-            E.line("  if (threadIdx.x < (kp.many_n ? kp.many_n : 1u)) obr_[threadIdx.x] = kp.many_n ? cget(kp.many, threadIdx.x) : BatchRef{kp.pkt_data, kp.pkt_off, kp.pkt_len, kp.r0, kp.status, kp.steps, kp.err_pc, 0};");
+            E.line("  if (threadIdx.x < (kp.many_n ? kp.many_n : 1u)) obr_[threadIdx.x] = kp.many_n ? cget(kp.many, threadIdx.x) : BatchRef{kp.pkt_data, kp.pkt_off, kp.pkt_len, kp.r0, kp.status, kp.steps, kp.err_pc, kp.pkt_stride | (uint64_t)kp.pkt_len_all << 32};");
             E.line("  __syncthreads();");
             E.line("  uint32_t srow_ = orow_, sbase_ = 0;");
             // the row words this thread adds into at the end, loaded now (their round trip overlaps
@@ -512,7 +513,15 @@ class Gen {
             E.line("  const uint32_t nb_ = kp.many_n ? kp.many_n : 1u;");
             E.line("  bool bpre_ = false;   // this batch's first descriptor came with the previous batch's last packet");
             E.line("  for (uint32_t bt_ = 0; bt_ < nb_; bt_++) {");
-            E.line("  const BatchRef br_ = kp.many_n ? cget(kp.many, bt_) : BatchRef{kp.pkt_data, kp.pkt_off, kp.pkt_len, kp.r0, kp.status, kp.steps, kp.err_pc, 0};");
+            E.line("  const BatchRef br_ = kp.many_n ? cget(kp.many, bt_) : BatchRef{kp.pkt_data, kp.pkt_off, kp.pkt_len, kp.r0, kp.status, kp.steps, kp.err_pc, kp.pkt_stride | (uint64_t)kp.pkt_len_all << 32};");
+            // A uniform batch (null pkt_off / pkt_len) issues no descriptor load: the offset is the
+            // packet's index times the batch's stride, the length its one length.  The two scalars
+            // live in VGPRs (the loop has those to spare, not SGPRs: DESIGN 6.2); which form the batch
+            // has goes into ofl_ (4: no pkt_off, 8: no pkt_len), and the packet loop tests a copy pinned
+            // per packet (a hoisted test would hold a lane mask, two SGPRs, across the loop).
+            E.line("  uint32_t cstr_ = (uint32_t)br_.compact, clen_ = (uint32_t)(br_.compact >> 32);");
+            E.line("  asm volatile(\"\" : \"+v\"(cstr_), \"+v\"(clen_));");
+            E.line("  ofl_ = (ofl_ & 3u) | (br_.pkt_off ? 0u : 4u) | (br_.pkt_len ? 0u : 8u);");
         }
         if (lpf_on) {
             const uint32_t D = kLpfD, XW = xpf.words;
@@ -526,7 +535,7 @@ class Gen {
             for (uint32_t d = 0; d < D; d++) {
                 E.line("    const uint32_t lx%u_ = pkt_index(kp, g, %uu, ex_begin, ex_count);", d, d);
                 E.line("    uint64_t lo%u_ = 0; uint32_t ll%u_ = 0;", d, d);
-                E.line("    if (lx%u_ != NO_PKT) { lo%u_ = *gp(kp.pkt_off + lx%u_); ll%u_ = *gp(kp.pkt_len + lx%u_); }", d, d, d, d, d);
+                E.line("    if (lx%u_ != NO_PKT) { lo%u_ = pkt_off_at(kp, lx%u_); ll%u_ = pkt_len_at(kp, lx%u_); }", d, d, d, d, d);
             }
             for (uint32_t d = 0; d < D; d++) {
                 for (uint32_t q = 0; q < XW; q++) E.line("    uint64_t lw%u_%u_ = 0;", d, q);
@@ -551,20 +560,26 @@ class Gen {
             E.line("  uint64_t noff_ = 0, noff2_ = 0; uint32_t nlen_ = 0, nlen2_ = 0, nidx_ = NO_PKT, nidx2_ = NO_PKT, xn_ok_ = 0u, xc_ok_ = 0u;");
             for (uint32_t q = 0; q < xpf.words; q++) E.line("  uint64_t xn%u_ = 0;", q);
             E.line("  nidx_ = pkt_index(kp, g, 0u, ex_begin, ex_count);");
-            E.line("  if (nidx_ != NO_PKT) { noff_ = *gp(kp.pkt_off + nidx_); nlen_ = *gp(kp.pkt_len + nidx_); }");
+            E.line("  if (nidx_ != NO_PKT) { noff_ = pkt_off_at(kp, nidx_); nlen_ = pkt_len_at(kp, nidx_); }");
             emit_xpf_issue("  ");
             E.line("  nidx2_ = nidx_ != NO_PKT ? pkt_next(kp, nidx_, 1u, ex_begin, ex_count) : NO_PKT;");
-            E.line("  if (nidx2_ != NO_PKT) { noff2_ = *gp(kp.pkt_off + nidx2_); nlen2_ = *gp(kp.pkt_len + nidx2_); }");
+            E.line("  if (nidx2_ != NO_PKT) { noff2_ = pkt_off_at(kp, nidx2_); nlen2_ = pkt_len_at(kp, nidx2_); }");
         } else if (pf) {
             if (spread_own)
-                E.line("  if (!bpre_ && oi_ != NO_PKT) { poff_ = *gp(br_.pkt_off + oi_); plen_ = *gp(br_.pkt_len + oi_); } bpre_ = false;");
+            {   // the batch's first descriptor: computed, or prefetched by the batch before, or loaded now
+                E.line("  if (oi_ != NO_PKT) {");
+                E.line("    if (!bpre_) { pkt_off_pf(!(ofl_ & 4u), br_.pkt_off, oi_, noff_); pkt_len_pf(!(ofl_ & 8u), br_.pkt_len, oi_, nlen_); }");
+                E.line("    poff_ = pkt_off_take(!(ofl_ & 4u), noff_, cstr_, oi_); plen_ = pkt_len_take(!(ofl_ & 8u), nlen_, clen_);");
+                E.line("  }");
+                E.line("  bpre_ = false;");
+            }
             else
                 E.line("  uint64_t noff_ = 0; uint32_t nlen_ = 0;");
             if (spread_own) {
             } else if (spread_on)
-                E.line("  { const uint32_t n_ = blo_ + threadIdx.x; if (n_ < bhi_) { noff_ = *gp(kp.pkt_off + n_); nlen_ = *gp(kp.pkt_len + n_); } }");
+                E.line("  { const uint32_t n_ = blo_ + threadIdx.x; if (n_ < bhi_) pkt_desc_pf(kp, n_, noff_, nlen_); }");
             else
-                E.line("  { const uint32_t n_ = pkt_index(kp, g, 0u, ex_begin, ex_count); if (n_ != NO_PKT) { noff_ = *gp(kp.pkt_off + n_); nlen_ = *gp(kp.pkt_len + n_); } }");
+                E.line("  { const uint32_t n_ = pkt_index(kp, g, 0u, ex_begin, ex_count); if (n_ != NO_PKT) pkt_desc_pf(kp, n_, noff_, nlen_); }");
         }
         if (spread_own) {
             E.line("  uint32_t oni_ = oi_;   // the thread's next packet");
@@ -595,7 +610,7 @@ class Gen {
             for (uint32_t q = 0; q < xpf.words; q++)
                 E.line("      if (xc_ok_) xc%u_ = lpfw_[(j * %uu + %uu) * 256u + threadIdx.x];", q, xpf.words, q);
             E.line("    } else {");
-            E.line("      poff_ = *gp(kp.pkt_off + i); plen_ = *gp(kp.pkt_len + i); xc_ok_ = 0u;");
+            E.line("      poff_ = pkt_off_at(kp, i); plen_ = pkt_len_at(kp, i); xc_ok_ = 0u;");
             E.line("    }");
         } else if (pf && xpf.on) {
             E.line("    const uint64_t poff_ = noff_; const uint32_t plen_ = nlen_;");
@@ -604,15 +619,26 @@ class Gen {
             E.line("    noff_ = noff2_; nlen_ = nlen2_; nidx_ = nidx2_;");
             emit_xpf_issue("    ");
             E.line("    nidx2_ = nidx_ != NO_PKT ? pkt_next(kp, nidx_, j + 2u, ex_begin, ex_count) : NO_PKT;");
-            E.line("    if (nidx2_ != NO_PKT) { noff2_ = *gp(kp.pkt_off + nidx2_); nlen2_ = *gp(kp.pkt_len + nidx2_); }");
+            E.line("    if (nidx2_ != NO_PKT) { noff2_ = pkt_off_at(kp, nidx2_); nlen2_ = pkt_len_at(kp, nidx2_); }");
         } else if (pf) {
-            if (!spread_own) E.line("    const uint64_t poff_ = noff_; const uint32_t plen_ = nlen_;");
+            if (!spread_own) E.line("    const uint64_t poff_ = pkt_off_take(kp, noff_, i); const uint32_t plen_ = pkt_len_take(kp, nlen_);");
             if (spread_own) {
-                E.line("    if (j + 1u < oQ_) { if (oni_ != NO_PKT) { noff_ = *gp(br_.pkt_off + oni_); nlen_ = *gp(br_.pkt_len + oni_); } }");
-                E.line("    else if (bt_ + 1u < nb_ && oi_ != NO_PKT) { const BatchRef &nx_ = obr_[bt_ + 1u]; noff_ = *gp(nx_.pkt_off + oi_); nlen_ = *gp(nx_.pkt_len + oi_); bpre_ = true; }");
+                // (a uniform batch prefetches nothing: its next descriptor is computed at L_term; at a
+                // batch boundary the next batch's form decides, read with its arrays from LDS)
+                E.line("    uint32_t cf_ = ofl_; asm volatile(\"\" : \"+s\"(cf_));");
+                // One load site and one mask for both cases, as before: the two addresses are chosen
+                // first, and both loads are made when the batch has either array.  An array the batch
+                // does not have (one of the two only) is read from the kernarg segment instead, 8 valid
+                // bytes whose value pkt_*_take never looks at.
+                E.line("    const uint64_t *po_ = nullptr; const uint32_t *pl_ = nullptr;");
+                E.line("    if (j + 1u < oQ_) { if (oni_ != NO_PKT && (cf_ & 12u) != 12u) { po_ = (cf_ & 4u) ? (const uint64_t *)&kp : br_.pkt_off + oni_; pl_ = (cf_ & 8u) ? (const uint32_t *)&kp : br_.pkt_len + oni_; } }");
+                E.line("    else if (bt_ + 1u < nb_ && oi_ != NO_PKT) { const BatchRef &nx_ = obr_[bt_ + 1u];");
+                E.line("      if (nx_.pkt_off || nx_.pkt_len) { po_ = nx_.pkt_off ? nx_.pkt_off + oi_ : (const uint64_t *)&kp; pl_ = nx_.pkt_len ? nx_.pkt_len + oi_ : (const uint32_t *)&kp; }");
+                E.line("      bpre_ = true; }");
+                E.line("    if (po_) { pkt_off_pf(true, po_, 0u, noff_); pkt_len_pf(true, pl_, 0u, nlen_); }");
             }
-            else if (spread_on) E.line("    { const uint32_t n_ = i + 256u; if (n_ < bhi_) { noff_ = *gp(kp.pkt_off + n_); nlen_ = *gp(kp.pkt_len + n_); } }");
-            else E.line("    { const uint32_t n_ = pkt_next(kp, i, j + 1, ex_begin, ex_count); if (n_ != NO_PKT) { noff_ = *gp(kp.pkt_off + n_); nlen_ = *gp(kp.pkt_len + n_); } }");
+            else if (spread_on) E.line("    { const uint32_t n_ = i + 256u; if (n_ < bhi_) pkt_desc_pf(kp, n_, noff_, nlen_); }");
+            else E.line("    { const uint32_t n_ = pkt_next(kp, i, j + 1, ex_begin, ex_count); if (n_ != NO_PKT) pkt_desc_pf(kp, n_, noff_, nlen_); }");
         }
         E.line("    const KParams &kq_ = kp;");   // the once-per-packet fields' name in the generated text
         if (spread_own) {   // the packet's vCPU and its row of the spread map (chunked: per packet)
@@ -639,7 +665,7 @@ class Gen {
             if (spread_own) {   // a plain launch (ofl_ = 0): no room, no array; only the interface scalars
                 E.line("    uint32_t H = 0u, T = 0u;");
                 E.line("    L.ingress = oin_; L.rxq = orx_; L.egress = oeg_;");
-                E.line("    if (ofl_) {");
+                E.line("    if (ofl_ & 3u) {");
                 E.line("      H = kq_.headroom_arr ? ld_nt(kq_.headroom_arr + i) : kq_.headroom;");
                 E.line("      T = kq_.tailroom_arr ? ld_nt(kq_.tailroom_arr + i) : kq_.tailroom;");
                 E.line("      if (kq_.ingress_arr) L.ingress = (uint32_t)ld_nt(kq_.ingress_arr + i);");
@@ -654,16 +680,16 @@ class Gen {
                 E.line("    const uint32_t len = plen_;");
                 E.line("    L.pkt = %s + poff_;", spread_own ? "br_.pkt_data" : "kq_.pkt_data");
             } else if (spread_own) {
-                E.line("    const uint32_t len = *gp(br_.pkt_len + i);");
-                E.line("    L.pkt = br_.pkt_data + *gp(br_.pkt_off + i);");
+                E.line("    const uint32_t len = pkt_len_at(!(ofl_ & 8u), br_.pkt_len, clen_, i);");
+                E.line("    L.pkt = br_.pkt_data + pkt_off_at(!(ofl_ & 4u), br_.pkt_off, cstr_, i);");
             } else {
-                E.line("    const uint32_t len = *gp(kq_.pkt_len + i);");
-                E.line("    L.pkt = kq_.pkt_data + *gp(kq_.pkt_off + i);");
+                E.line("    const uint32_t len = pkt_len_at(kq_, i);");
+                E.line("    L.pkt = kq_.pkt_data + pkt_off_at(kq_, i);");
             }
             E.line("    L.M = H + len + T;");
             E.line("    L.pa = P;");
             E.line("    L.rec = nullptr;");
-            if (spread_own) E.line("    if (ofl_) {");   // (no rooms to zero in a plain launch)
+            if (spread_own) E.line("    if (ofl_ & 3u) {");   // (no rooms to zero in a plain launch)
             E.line("    for (uint32_t b = 0; b < H; b++) *gp(L.pkt + b) = 0;");
             E.line("    for (uint32_t b = 0; b < T; b++) *gp(L.pkt + H + len + b) = 0;");
             if (spread_own) E.line("    }");
@@ -731,7 +757,10 @@ class Gen {
         // the owned form takes the next packet's descriptor here, ahead of the result stores: the
         // wait for it (it came back with this packet's first loads) is the last one before the next
         // packet's window loads, which the stores' acknowledgements then travel with
-        if (spread_own && pf) E.line("    poff_ = noff_; plen_ = nlen_; asm volatile(\"\" : \"+v\"(poff_), \"+v\"(plen_));");
+        // (a uniform batch: index * stride and the one length instead; after a batch's last packet the
+        // next batch's top sets both)
+        // (the form bits pinned again here: a copy held from the loop top would be one more live SGPR)
+        if (spread_own && pf) E.line("    { uint32_t ct_ = ofl_; asm volatile(\"\" : \"+s\"(ct_)); poff_ = pkt_off_take(!(ct_ & 4u), noff_, cstr_, oni_); plen_ = pkt_len_take(!(ct_ & 8u), nlen_, clen_); asm volatile(\"\" : \"+v\"(poff_), \"+v\"(plen_)); }");
         E.line("    {");
         {   // the owned form's results go to the batch of this iteration, its addresses read from the
             // block's LDS copy of the batch references (obr_): no SGPR holds them across the loop

@@ -173,7 +173,7 @@ struct BatchRef {
     uint8_t *status;
     uint32_t *steps;
     int32_t *err_pc;
-    uint64_t pad;
+    uint64_t compact;   // pkt_stride | (uint64_t)pkt_len_all << 32: what a null pkt_off / pkt_len stands for
 };
 
 struct KParams {
@@ -249,9 +249,11 @@ struct KParams {
     struct DeferRec *defer;
     uint32_t *defer_any;
     uint32_t defer_epoch;
-    // (reserved: the by-value kernarg layout is part of every JIT kernel's code, so the fields
-    // after this word keep their offsets -- see the static_asserts after the struct)
-    uint32_t reserved0;
+    // uniform batches (mimic_xdp_batch.pkt_stride): with pkt_off null, packet memory i starts at
+    // pkt_data + i * pkt_stride.  (In the word that was reserved: the by-value kernarg layout is part
+    // of every JIT kernel's code, so the fields after it keep their offsets -- see the static_asserts
+    // after the struct.)
+    uint32_t pkt_stride;
     // spread launches (jit.cpp analyze_spread): a vCPU's packets run on many lanes; a generic
     // access that reaches per-CPU map memory would break that mode's exactness and sets *spread_bad
     // (never cleared: the host reports it as an engine error).  nullptr in every other launch.
@@ -276,6 +278,9 @@ struct KParams {
     // multi-batch owned launches (mimic_run_xdp_many): many_n batches, run one after another by
     // every thread (0: the one batch above)
     uint32_t many_n;
+    // uniform batches (mimic_xdp_batch.pkt_len_all): with pkt_len null, every packet's length (in
+    // what was the padding ahead of many[])
+    uint32_t pkt_len_all;
     struct BatchRef many[MIMIC_MANY_MAX];
     // single-process stepping: the process's first launch copies its NewProcess image (pinned,
     // device-mapped host memory) into its device block itself (no copy ahead of the launch), and
@@ -290,8 +295,10 @@ struct KParams {
 };
 // JIT kernels take KParams by value: its layout is part of their machine code
 static_assert(sizeof(KParams) == 968, "KParams: the kernarg layout of every JIT kernel");
-static_assert(__builtin_offsetof(KParams, reserved0) == 356 && __builtin_offsetof(KParams, spread_bad) == 360,
-              "KParams: the fields around the reserved word keep their offsets");
+static_assert(__builtin_offsetof(KParams, pkt_stride) == 356 && __builtin_offsetof(KParams, spread_bad) == 360,
+              "KParams: the fields around the once reserved word keep their offsets");
+static_assert(__builtin_offsetof(KParams, pkt_len_all) + 4 == __builtin_offsetof(KParams, many),
+              "KParams: pkt_len_all fills the padding ahead of many[]");
 
 // A process a JIT lane suspended at a slow path (defer mode): the registers the slot and its
 // successors can read, the slot (PC) and program, the steps before the slot, the process's

@@ -131,6 +131,29 @@ DEV uint32_t ctx_done(const KParams &kp, uint32_t i) {
 template <typename T>
 DEV const GAS T *gp(const T *p) { return (const GAS T *)p; }
 
+// Packet i's descriptor: every reader of a batch's pkt_off / pkt_len goes through these.  A null
+// array stands for a uniform batch (mimic_xdp_batch.pkt_stride / pkt_len_all): the value is then
+// arithmetic on the index and no load is issued.  The null test is uniform for the batch.
+// (`arr`: the array exists -- its null test, or the caller's copy of it, as the owned kernels' ofl_ bits)
+DEV uint64_t pkt_off_at(bool arr, const uint64_t *off, uint32_t stride, uint32_t i) { return arr ? *gp(off + i) : (uint64_t)i * stride; }
+DEV uint32_t pkt_len_at(bool arr, const uint32_t *len, uint32_t len_all, uint32_t i) { return arr ? *gp(len + i) : len_all; }
+// The same in two halves for the kernels that prefetch a descriptor a packet ahead: pkt_*_pf issues
+// the load into the prefetch register (nothing for a uniform batch), pkt_*_take gives the descriptor
+// where the packet starts.  The prefetch register is only ever written by loads: merged with computed
+// values it would cost a vmcnt wait where the load is issued.
+DEV void pkt_off_pf(bool arr, const uint64_t *off, uint32_t i, uint64_t &pf) { if (arr) pf = *gp(off + i); }
+DEV void pkt_len_pf(bool arr, const uint32_t *len, uint32_t i, uint32_t &pf) { if (arr) pf = *gp(len + i); }
+DEV uint64_t pkt_off_take(bool arr, uint64_t pf, uint32_t stride, uint32_t i) { return arr ? pf : (uint64_t)i * stride; }
+DEV uint32_t pkt_len_take(bool arr, uint32_t pf, uint32_t len_all) { return arr ? pf : len_all; }
+DEV void pkt_desc_pf(const KParams &kp, uint32_t i, uint64_t &off_pf, uint32_t &len_pf) {
+    pkt_off_pf(kp.pkt_off != nullptr, kp.pkt_off, i, off_pf);
+    pkt_len_pf(kp.pkt_len != nullptr, kp.pkt_len, i, len_pf);
+}
+DEV uint64_t pkt_off_take(const KParams &kp, uint64_t pf, uint32_t i) { return pkt_off_take(kp.pkt_off != nullptr, pf, kp.pkt_stride, i); }
+DEV uint32_t pkt_len_take(const KParams &kp, uint32_t pf) { return pkt_len_take(kp.pkt_len != nullptr, pf, kp.pkt_len_all); }
+DEV uint64_t pkt_off_at(const KParams &kp, uint32_t i) { return pkt_off_at(kp.pkt_off != nullptr, kp.pkt_off, kp.pkt_stride, i); }
+DEV uint32_t pkt_len_at(const KParams &kp, uint32_t i) { return pkt_len_at(kp.pkt_len != nullptr, kp.pkt_len, kp.pkt_len_all, i); }
+
 // index of the j-th packet lane g runs under the batch's schedule, or NO_PKT
 #define NO_PKT 0xffffffffu
 DEV uint32_t pkt_index(const KParams &kp, uint32_t g, uint32_t j, uint32_t ex_begin, uint32_t ex_count) {
@@ -1012,7 +1035,7 @@ DEV uint64_t skb_leak_pre(const KParams &kp, uint32_t i) {
 // the resume kernel re-attaches -- its record, rooms and packet are what the JIT lane left.
 DEV int skb_load(const KParams &kp, Lane &L, uint32_t i, uint64_t &r1, bool attach_only = false) {
     SkbRec *rec = kp.skb_rec + i;
-    L.pkt = kp.pkt_data + kp.pkt_off[i];
+    L.pkt = kp.pkt_data + pkt_off_at(kp, i);
     const uint64_t pf = kp.skb_prefix[i];
     if (kp.skb_drv && !attach_only)   // the prep kernel's derived words into the record
         for (uint32_t q = 0; q < SKB_DERIVED_Q; q++) ((uint64_t *)rec)[q] = kp.skb_drv[(size_t)i * SKB_DERIVED_Q + q];
@@ -1063,7 +1086,7 @@ DEV int skb_attach(const KParams &kp, Lane &L, uint32_t i, uint64_t &r1, uint64_
 // the packet offset and the leak prefix are loaded together (one memory round trip, not the
 // record length first and the rest after it), then the record goes to LDS.
 DEV int skb_load_lds(const KParams &kp, Lane &L, uint32_t i, uint64_t &r1, uint64_t *d) {
-    const uint64_t po = kp.pkt_off[i];
+    const uint64_t po = pkt_off_at(kp, i);
     // the packet's derived words: 96 contiguous bytes of the prep kernel's compact array (consecutive
     // lanes, consecutive records), six 16-byte loads
     typedef uint64_t u64x2a __attribute__((ext_vector_type(2)));

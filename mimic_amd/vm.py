@@ -983,18 +983,57 @@ class Process:
 # ---------------------------------------------------------------------------------------------
 
 class XDPBatch:
-    """A batch of xdp_md contexts resident on the GPU (see mimic_xdp_batch)."""
+    """A batch of xdp_md contexts resident on the GPU (see mimic_xdp_batch).
+
+    A uniform batch carries no per-packet descriptors: pkt_off=None with a pkt_stride (packet memory
+    i at pkt_base + i * pkt_stride of pkt_data), pkt_len=None with a pkt_len_all and an explicit n.
+    The constructor keeps what it is given; from_numpy / from_packets drop an array only when the
+    host array they were handed proves it redundant, and a dropped array does not exist on the
+    batch afterwards (there is nothing to edit in place and have go unnoticed)."""
 
     def __init__(self, pkt_data, pkt_off, pkt_len, headroom=0, tailroom=0, ingress=0, rxq=0, egress=0,
-                 schedule=L.SCHED_CHUNKED, cpu=None, step_budget=0):
+                 schedule=L.SCHED_CHUNKED, cpu=None, step_budget=0, pkt_stride=0, pkt_len_all=0, n=None,
+                 pkt_base=0):
         self.pkt_data, self.pkt_off, self.pkt_len = pkt_data, pkt_off, pkt_len
         self.headroom, self.tailroom = headroom, tailroom
         self.ingress, self.rxq, self.egress = ingress, rxq, egress
         self.schedule, self.cpu, self.step_budget = schedule, cpu, step_budget
+        # pkt_base: byte offset of packet memory 0 in pkt_data when pkt_off is None (the first
+        # offset, folded into the data pointer the engine is given)
+        self.pkt_stride, self.pkt_len_all, self.pkt_base = int(pkt_stride), int(pkt_len_all), int(pkt_base)
+        if pkt_off is not None and self.pkt_base:
+            raise ValueError("pkt_base is for batches without pkt_off")
+        if n is None:
+            if pkt_len is None and pkt_off is None:
+                raise ValueError("a batch without pkt_off and pkt_len needs an explicit n")
+            n = int((pkt_len if pkt_len is not None else pkt_off).numel())
+        self._n = int(n)
+        for a in (pkt_off, pkt_len):
+            if a is not None and int(a.numel()) != self._n:
+                raise ValueError("pkt_off / pkt_len and n disagree")
+        if not (0 <= self.pkt_stride < 1 << 32 and 0 <= self.pkt_len_all < 1 << 32):
+            raise ValueError("pkt_stride and pkt_len_all are 32-bit")   # (stride 0 with n > 1: the engine's EINVAL)
 
     @property
     def n(self) -> int:
-        return int(self.pkt_len.numel())
+        return self._n
+
+    def offset(self, i: int) -> int:
+        """Byte offset of packet memory i in pkt_data."""
+        if self.pkt_off is None:
+            return self.pkt_base + i * self.pkt_stride
+        return int(self.pkt_off[i].item())
+
+    def length(self, i: int) -> int:
+        return self.pkt_len_all if self.pkt_len is None else int(self.pkt_len[i].item())
+
+    def offsets(self):
+        """Every packet memory's byte offset in pkt_data (host numpy array)."""
+        import numpy as np
+
+        if self.pkt_off is None:
+            return self.pkt_base + np.arange(self._n, dtype=np.int64) * self.pkt_stride
+        return self.pkt_off.cpu().numpy()
 
     def _c(self):
         """The mimic_xdp_batch of this batch (built once; a batch is not modified after use)."""
@@ -1006,9 +1045,11 @@ class XDPBatch:
         b = L.XDPBatch()
         b.n = self.n
         b.schedule = self.schedule
-        b.pkt_data = self.pkt_data.data_ptr()
-        b.pkt_off = self.pkt_off.data_ptr()
-        b.pkt_len = self.pkt_len.data_ptr()
+        b.pkt_data = self.pkt_data.data_ptr() + (self.pkt_base if self.pkt_off is None else 0)
+        b.pkt_off = self.pkt_off.data_ptr() if self.pkt_off is not None else None
+        b.pkt_len = self.pkt_len.data_ptr() if self.pkt_len is not None else None
+        b.pkt_stride = self.pkt_stride if self.pkt_off is None else 0
+        b.pkt_len_all = self.pkt_len_all if self.pkt_len is None else 0
         b.headroom = self.headroom.data_ptr() if isinstance(self.headroom, torch.Tensor) else None
         b.headroom_all = 0 if isinstance(self.headroom, torch.Tensor) else int(self.headroom)
         b.tailroom = self.tailroom.data_ptr() if isinstance(self.tailroom, torch.Tensor) else None
@@ -1079,19 +1120,36 @@ class XDPBatch:
         def opt(v, dt):
             return v if np.isscalar(v) else t(v, dt)
 
-        return cls(t(buf, np.uint8), t(np.asarray(off, dtype=np.uint64).view(np.int64), np.int64),
-                   t(np.asarray(lens, dtype=np.uint32).view(np.int32), np.int32),
+        # A descriptor array the host array proves redundant is not uploaded at all (the kernels then
+        # load no descriptor for the packet): offsets off[0] + i * s with 0 < s < 2^32 (off[0] goes
+        # into the data pointer), lengths all equal.  n <= 1 keeps its arrays; MIMIC_BATCH_COMPACT=0
+        # keeps every array (how the array path is measured on the same kernel).
+        off64 = np.ascontiguousarray(np.asarray(off, dtype=np.uint64))
+        len32 = np.ascontiguousarray(np.asarray(lens, dtype=np.uint32))
+        n = int(len32.shape[0])
+        compact = n > 1 and off64.shape[0] == n and os.environ.get("MIMIC_BATCH_COMPACT", "1") != "0"
+        stride = base = len_all = 0
+        drop_off = drop_len = False
+        if compact:
+            s = int(off64[1]) - int(off64[0])
+            if 0 < s < 1 << 32 and bool((off64 == off64[0] + np.arange(n, dtype=np.uint64) * np.uint64(s)).all()):
+                drop_off, stride, base = True, s, int(off64[0])
+            if bool((len32 == len32[0]).all()):
+                drop_len, len_all = True, int(len32[0])
+        return cls(t(buf, np.uint8), None if drop_off else t(off64.view(np.int64), np.int64),
+                   None if drop_len else t(len32.view(np.int32), np.int32),
                    opt(headroom, np.int32), opt(tailroom, np.int32), opt(ingress, np.int32), opt(rxq, np.int32),
-                   opt(egress, np.int32), schedule, cpu, step_budget)
+                   opt(egress, np.int32), schedule, cpu, step_budget, pkt_stride=stride, pkt_len_all=len_all, n=n,
+                   pkt_base=base)
 
     def packet_bytes(self, i: int) -> bytes:
         """Packet memory i (H+L+T bytes) as it is now on the device."""
         import numpy as np
 
-        o = int(self.pkt_off[i].item())
+        o = self.offset(i)
         h = int(self.headroom[i].item()) if not np.isscalar(self.headroom) else int(self.headroom)
         t_ = int(self.tailroom[i].item()) if not np.isscalar(self.tailroom) else int(self.tailroom)
-        n = h + int(self.pkt_len[i].item()) + t_
+        n = h + self.length(i) + t_
         return bytes(self.pkt_data[o:o + n].cpu().numpy().tobytes())
 
 
@@ -1551,7 +1609,7 @@ class ProcessPool:
         cpp = [j.Context for j in js] if any(j.Context is not None for j in js) else None
         res = self.vm.RunXDPBatch(pid, batch, ctx_per_packet=cpp).numpy(len(js))
         mem = batch.pkt_data.cpu().numpy()
-        offs = batch.pkt_off.cpu().numpy()
+        offs = batch.offsets()
         for k, j in enumerate(js):
             p = j.Process
             p.Registers.R0 = int(res["r0"][k]) & 0xFFFFFFFFFFFFFFFF
