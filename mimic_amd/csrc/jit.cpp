@@ -138,16 +138,13 @@ class Gen {
         max_n = mx;
     }
 
-    bool careful_copies = true;
-    uint32_t max_n = 0;
+    // ---- the knobs (read in the constructor) and what the caller sets before source() ----
     bool fast_paths = true;    // MIMIC_JIT_FAST=0: every access through resolve()
     int cold_mode = 0;         // MIMIC_JIT_COLD: 0 auto, 1 call, 2 inline, 3 defer
     bool skb_fields = true;    // MIMIC_JIT_SKBFIELD=0: no per-field sk_buff access code
     bool skb_lds_knob = true;  // MIMIC_JIT_SKBLDS=0: no LDS copy of the sk_buff record
-    bool skb_lds = false;
     bool inc_knob = true;      // MIMIC_JIT_INC=0: no fused counter increments (fusable_inc)
     bool sm_lds_knob = true;   // MIMIC_JIT_SMLDS=0: stack validity masks in VGPRs in defer mode too
-    static constexpr uint32_t kSrecQ = 21;   // 8-byte words per LDS record slot (SkbRec is 20)
     bool hash_fast = true;     // MIMIC_JIT_HASH=0: no inline hash-map lookups
     bool tail_inline = true;   // MIMIC_JIT_TAIL=0: no inline tail calls
     // An EXIT that pops a frame goes to its program's one return block (R<p>_) instead of carrying the
@@ -162,9 +159,7 @@ class Gen {
     bool window = true;        // MIMIC_JIT_WINDOW=0: no windowed early loads
     int speculate = 8;         // MIMIC_JIT_SPEC=N: at most N early packet loads per region (0: none)
     bool combine_knob = true;  // MIMIC_JIT_COMBINE=0: every wave reserves freelist positions with its own add
-    bool hash_combine = false;
     int hchunk_knob = 32;       // MIMIC_JIT_HCHUNK (hashmap.h MIMIC_HCHUNK; 0: off)
-    bool hash_chunk = false;    // the chunk map's positions come in per-block chunks (hashmap.h h_chunk_fill)
     bool ntres = true;         // MIMIC_JIT_NTRES=0: r0 / status stores not non-temporal (measured 1-3 % slower)
     bool forward = true;       // MIMIC_JIT_FWD=0: helper-1 keys always reread from the stack
     int waves = 0;             // MIMIC_JIT_WAVES=W: amdgpu_waves_per_eu(W) on the kernel
@@ -179,12 +174,16 @@ class Gen {
     // descriptor and window loads delays every first packet), the
     // chunked schedule 38.9 -> 36.8 us, cfg 3 / cfg 4 unchanged.
     bool lpf_knob = false;
-    bool lpf_on = false;
-    bool lds_stack_on = false;
     static constexpr uint32_t kLpfD = 4;
     bool vc_knob = true;       // MIMIC_JIT_VC=0: no lane value cache (analyze_vc)
     uint32_t lds_stack_q = 16; // MIMIC_JIT_LDSSTK=Q: LDS window over the top 8Q bytes of frame 0
-    bool vc_on = false;
+    // Tail calls jump between programs.  With a jump table at every tail-call site as well as at
+    // the entry, the programs form a cycle with several entries (irreducible control flow), which
+    // the AMDGPU backend must restructure -- at a large register cost (cfg 5: 282 VGPRs without
+    // the slow paths).  One dispatch block (D_) that the entry and every tail call go through
+    // keeps the cycle single-entry.  MIMIC_JIT_DISPATCH=0: the per-site jump tables.
+    bool dispatch_knob = true;
+    uint32_t ctx = CTX_XDP;    // the batch context this kernel is generated for
     const SpreadReq *spread_req = nullptr;   // the VM's per-CPU arrays: spread mode is possible (analyze_spread)
     bool ctx_check = false;   // the kernel reads each packet's Run(ctx) context before its first step
     // The single-process form (Process.Run of one process, engine.cpp process_advance): every exit
@@ -192,21 +191,24 @@ class Gen {
     // program and the steps into KParams::step.  No fused counter increments: their register is
     // dead for the rest of the program, not after it (Run leaves every register readable).
     bool proc = false;
-    bool spread_on = false;
-    bool spread_own = false;   // the owned form (SpreadReq::own): every packet of a block's vCPUs in the block
-    uint32_t spread_map = 0, spread_n = 0, spread_row = 0;   // the counted map, counter width, E * S
     std::map<uint32_t, uint32_t> vc_ok;  // LD_IMM64 slots (kernel-wide) naming a per-CPU array whose row can be cached -> E * S
-    uint32_t vc_slot = 0;      // the LD_IMM64 slot (kernel-wide index) whose map hint names the cached map
-    uint32_t vc_rb = 0;        // its row bytes
-    bool vc_lds = false;       // the row is longer than four registers: an LDS slot per lane
-    // The cross-packet window prefetch (analyze_xpf): the entry program `prog` makes its first
-    // window of early loads at slot `hp` from register `base` = data + `off` - lo; the window's
-    // bytes lie at data offset `off` .. off + 8 * words of the packet.
-    struct Xpf {
-        bool on = false;
-        uint32_t prog = 0, hp = 0, base = 0, words = 0;
-        int64_t off = 0;
-    } xpf;
+
+    // ---- facts of the program set (the constructor) ----
+    bool careful_copies = true;
+    uint32_t max_n = 0;
+    bool has_tail() const { return any_tail; }
+    bool has_early_loads() const { return !spec_use.empty(); }
+    bool dispatch_on() const { return dispatch_knob && any_tail; }
+    std::string nonempty_cases() const {
+        std::string c;
+        for (auto &q : P)
+            if (q.n) c += "    case " + std::to_string(q.id) + "u:";
+        return c;
+    }
+
+    // ---- the decisions: plan() sets them, emission only reads them ----
+    uint32_t cold_sites = 0;
+    static constexpr uint32_t kColdInlineSites = 48;
     bool cold_inline = true;   // the cold paths are inlined at every site (else called or deferred)
     // Deferred slow paths (large kernels): a slow-path site stores the registers its slot and
     // the slots after it can read (analyze_live), the PC, program and steps into the lane's
@@ -217,26 +219,46 @@ class Gen {
     // cfg-5 chain need 380 VGPRs + AGPRs and 240 bytes of scratch at one wave per SIMD.
     bool defer_mode = false;
     std::vector<std::vector<uint16_t>> live;   // [prog][slot]: registers live into the slot
-    uint32_t cold_sites = 0;
-    static constexpr uint32_t kColdInlineSites = 48;
-    bool has_tail() const { return any_tail; }
-    bool has_early_loads() const { return !spec_use.empty(); }
-    // Tail calls jump between programs.  With a jump table at every tail-call site as well as at
-    // the entry, the programs form a cycle with several entries (irreducible control flow), which
-    // the AMDGPU backend must restructure -- at a large register cost (cfg 5: 282 VGPRs without
-    // the slow paths).  One dispatch block (D_) that the entry and every tail call go through
-    // keeps the cycle single-entry.  MIMIC_JIT_DISPATCH=0: the per-site jump tables.
-    bool dispatch_knob = true;
-    bool dispatch_on() const { return dispatch_knob && any_tail; }
-    std::string nonempty_cases() const {
-        std::string c;
-        for (auto &q : P)
-            if (q.n) c += "    case " + std::to_string(q.id) + "u:";
-        return c;
-    }
-    uint32_t ctx = CTX_XDP;    // the batch context this kernel is generated for
+    bool spread_on = false;
+    bool spread_own = false;   // the owned form (SpreadReq::own): every packet of a block's vCPUs in the block
+    uint32_t spread_map = 0, spread_n = 0, spread_row = 0;   // the counted map, counter width, E * S
+    bool vc_on = false;
+    uint32_t vc_slot = 0;      // the LD_IMM64 slot (kernel-wide index) whose map hint names the cached map
+    uint32_t vc_rb = 0;        // its row bytes
+    bool vc_lds = false;       // the row is longer than four registers: an LDS slot per lane
+    bool lds_stack_on = false;
+    static constexpr uint32_t kSrecQ = 21;   // 8-byte words per LDS record slot (SkbRec is 20)
+    bool skb_lds = false;
+    bool hash_writes = false, hash_deletes = false;   // some program updates or deletes / deletes
+    bool hash_combine = false;
+    bool hash_chunk = false;    // the chunk map's positions come in per-block chunks (hashmap.h h_chunk_fill)
+    bool pf = false;            // the next packet's descriptor is prefetched while this one runs
+    // The cross-packet window prefetch (analyze_xpf): the entry program `prog` makes its first
+    // window of early loads at slot `hp` from register `base` = data + `off` - lo; the window's
+    // bytes lie at data offset `off` .. off + 8 * words of the packet.
+    struct Xpf {
+        bool on = false;
+        uint32_t prog = 0, hp = 0, base = 0, words = 0;
+        int64_t off = 0;
+    } xpf;
+    bool lpf_on = false;
+    int waves_attr = 0;         // amdgpu_waves_per_eu on the kernel (0: the compiler's choice)
 
+    // The kernel's text: the decisions, the defines, then the one frame the program set takes.  The
+    // three frames share only the emit_* helpers below them, so a change to one form's prologue,
+    // loop or flush is made in that form's function.
     std::string source() {
+        plan();
+        emit_defines();
+        if (spread_own) emit_owned();
+        else if (spread_on) emit_spread();
+        else emit_one_lane();
+        return E.s;
+    }
+
+  private:
+    // Every decision, no output.
+    void plan() {
         // cold paths: inlined at each site for small kernels (best register allocation), called
         // for large ones (hipRTC time grows with every inlined copy)
         uint32_t sites = 0;
@@ -261,22 +283,50 @@ class Gen {
         spread_on = analyze_spread();
         spread_own = spread_on && spread_req->own;
         if (spread_on) vc_on = false;   // no lane owns a vCPU's row in a spread kernel
+        // the sk_buff records of the block's lanes in LDS (srec_)
+        skb_lds = ctx == CTX_SKB && fast_paths && skb_fields && skb_lds_knob;
         // the LDS stack window (runtime.h) when some stack store is made for real (not deferred
         // into a cold path, analyze_elide).  Measured: cfg 4 0.197 -> 0.179 ms per launch; the
         // sk_buff kernels keep their LDS for the SkbRec slots (with the window as well: cfg 5
         // 0.840 -> 0.848 ms)
-        const bool skb_lds_planned = ctx == CTX_SKB && fast_paths && skb_fields && skb_lds_knob;
-        if (lds_stack_q && fast_paths && !skb_lds_planned) {
-            bool any = false;
+        if (lds_stack_q && fast_paths && !skb_lds)
             for (auto &p : P)
                 for (uint32_t i = 0; i < p.n; i++) {
                     const DInsn &x = p.ins[i];
                     const uint32_t h = AUX_H(x.aux);
-                    if ((h == H_ST || h == H_STX) && insn_dst(x) == 10 && !elided.count({p.id, i})) any = true;
+                    if ((h == H_ST || h == H_STX) && insn_dst(x) == 10 && !elided.count({p.id, i})) lds_stack_on = true;
                 }
-            if (any) E.line("#define MIMIC_LDS_STACK_Q %u", lds_stack_q);
-            lds_stack_on = any;
-        }
+        for (auto &p : P)
+            for (uint32_t i = 0; i < p.n; i++)
+                if (AUX_H(p.ins[i].aux) == H_CALL) {   // helpers 2 and 3: map update and delete
+                    hash_writes |= (uint32_t)p.ins[i].k == 2 || (uint32_t)p.ins[i].k == 3;
+                    hash_deletes |= (uint32_t)p.ins[i].k == 3;
+                }
+        // inline inserts of a pop-only kernel: the block's waves combine their freelist
+        // reservations (hashmap.h h_comb_reserve); zeroed in the prologue
+        hash_combine = combine_knob && hash_writes && !hash_deletes && cold_inline && fast_paths;
+        // ... and the VM's chunk map takes them in per-block chunks (batch kernels only: every
+        // launch of one is followed by mimic_hash_compact_kernel, engine.cpp)
+        hash_chunk = hash_combine && !proc && hchunk_knob > 0;
+        // The packet loop is software-pipelined by one descriptor: packet j+1's index, offset and
+        // length are loaded while packet j runs (they travel with packet j's first loads), which
+        // takes one dependent HBM round trip off every packet after the first.
+        pf = ctx == CTX_XDP && prefetch;
+        if (!spec_use.empty() && !spread_on) analyze_xpf();
+        // (LDS budget: 4 blocks of 256 lanes per CU with the window alone; no other LDS user)
+        lpf_on = pf && xpf.on && lpf_knob && !xpf_knob && !spread_on && !vc_lds && !lds_stack_on && !defer_mode &&
+                 !hash_combine && lpf_safe();
+        if (!lpf_on && !xpf_knob) xpf.on = false;   // (the one-packet-ahead form only on request)
+        // Register budget: kernels small enough to inline their slow paths are built for 4 waves
+        // per SIMD -- 262 144 lanes then run in one round on the 1 024 SIMDs.  cfg 4 (169 VGPRs,
+        // 2 waves): 0.172 -> 0.137 ms per launch; cfg 2 and 3 fit 4 waves anyway.  Large kernels
+        // (cfg 5) keep the compiler's choice: forcing 2 waves there spills 264 VGPRs (1.2 vs 0.7 ms).
+        waves_attr = proc ? 0 : waves > 0 ? waves : (cold_inline ? 4 : 0);
+    }
+
+    // Everything ahead of the kernel's signature.
+    void emit_defines() {
+        if (lds_stack_on) E.line("#define MIMIC_LDS_STACK_Q %u", lds_stack_q);
         if (defer_mode && sm_lds_knob) E.line("#define MIMIC_SM_LDS 1");
         if (const char *dv = getenv("MIMIC_JIT_DEFS")) {   // measurement knob: "A,B=2" -> #define A / #define B 2
             std::string all(dv), d;
@@ -294,29 +344,14 @@ class Gen {
         if (spread_own) E.line("#define MIMIC_SPREAD_OWN 1");
         E.line("#define MIMIC_CTX_FIXED %u", ctx);
         E.line("#define MIMIC_COLD_INLINE %d", cold_inline ? 1 : 0);
-        {   // no program of the set updates or deletes: hash tables are read-only in every launch
-            // of this kernel (engine.cpp sets KParams.hash_ro from the same program set)
-            bool writes = false;
-            for (auto &p : P)
-                for (uint32_t i = 0; i < p.n; i++)
-                    if (AUX_H(p.ins[i].aux) == H_CALL && ((uint32_t)p.ins[i].k == 2 || (uint32_t)p.ins[i].k == 3)) writes = true;
-            E.line("#define MIMIC_HASH_RO %d", writes ? 0 : 1);
-            // no program of the set deletes: every launch of the kernel is pop-only (engine.cpp
-            // KParams.hash_pop_only from the same programs), so only the lock-free insert is built
-            bool deletes = false;
-            for (auto &p : P)
-                for (uint32_t i = 0; i < p.n; i++)
-                    if (AUX_H(p.ins[i].aux) == H_CALL && (uint32_t)p.ins[i].k == 3) deletes = true;
-            E.line("#define MIMIC_HASH_POPONLY %d", deletes ? 0 : 1);
-            // inline inserts of a pop-only kernel: the block's waves combine their freelist
-            // reservations (hashmap.h h_comb_reserve); zeroed in the prologue
-            hash_combine = combine_knob && writes && !deletes && cold_inline && fast_paths;
-            if (hash_combine) E.line("#define MIMIC_HASH_COMBINE 1");
-            // ... and the VM's chunk map takes them in per-block chunks (batch kernels only: every
-            // launch of one is followed by mimic_hash_compact_kernel, engine.cpp)
-            hash_chunk = hash_combine && !proc && hchunk_knob > 0;
-            if (hash_chunk) E.line("#define MIMIC_HASH_CHUNK 1\n#define MIMIC_HCHUNK %uu", (uint32_t)hchunk_knob);
-        }
+        // no program of the set updates or deletes: hash tables are read-only in every launch
+        // of this kernel (engine.cpp sets KParams.hash_ro from the same program set)
+        E.line("#define MIMIC_HASH_RO %d", hash_writes ? 0 : 1);
+        // no program of the set deletes: every launch of the kernel is pop-only (engine.cpp
+        // KParams.hash_pop_only from the same programs), so only the lock-free insert is built
+        E.line("#define MIMIC_HASH_POPONLY %d", hash_deletes ? 0 : 1);
+        if (hash_combine) E.line("#define MIMIC_HASH_COMBINE 1");
+        if (hash_chunk) E.line("#define MIMIC_HASH_CHUNK 1\n#define MIMIC_HCHUNK %uu", (uint32_t)hchunk_knob);
         E.line("#include \"runtime.h\"");
         if (spread_on) {
             // the block's counter table: one row of SPREAD_ROWW counters per vCPU its packets run on
@@ -356,13 +391,351 @@ class Gen {
             E.line("#define VC_FLUSH() do { if (vcd_) { vc_writeback(vcp_, vcb_, vc0_, vc1_, vc2_, vc3_); vcd_ = 0u; } vcv_ = 0u; } while (0)");
         else
             E.line("#define VC_FLUSH() do { } while (0)");
-        // Register budget: kernels small enough to inline their slow paths are built for 4 waves
-        // per SIMD -- 262 144 lanes then run in one round on the 1 024 SIMDs.  cfg 4 (169 VGPRs,
-        // 2 waves): 0.172 -> 0.137 ms per launch; cfg 2 and 3 fit 4 waves anyway.  Large kernels
-        // (cfg 5) keep the compiler's choice: forcing 2 waves there spills 264 VGPRs (1.2 vs 0.7 ms).
-        const int wv = proc ? 0 : waves > 0 ? waves : (cold_inline ? 4 : 0);
+    }
+
+    // ---- the one-lane kernel: lane g runs its vCPU's packets in order ----
+    void emit_one_lane() {
+        emit_kernel_open("kp.lanes");
+        E.line("  if (g >= kp.lanes) return;");
+        emit_lane_open();
+        E.line("  L.cpu = lane_cpu(kp, g);");
+        if (vc_on) emit_vc_open();
+        emit_locals();
+        // the first packet's descriptor
+        if (lpf_on) emit_lpf_park();
+        else if (pf && xpf.on) emit_xpf_first();
+        else if (pf) emit_pf_first("pkt_index(kp, g, 0u, ex_begin, ex_count)", "n_ != NO_PKT");
+        E.line("  for (uint32_t j = 0; j < kp.per_lane; j++) {");
+        E.line("    uint32_t i;");
+        E.line("    if (kp.sched == SCHED_CHUNKED) { const uint64_t ii = (uint64_t)g * kp.per_lane + j; if (ii >= kp.n) break; i = (uint32_t)ii; }");
+        E.line("    else if (kp.sched == SCHED_INTERLEAVED) { const uint64_t ii = (uint64_t)j * kp.lanes + (g >= kp.sched_shift ? g - kp.sched_shift : g + kp.lanes - kp.sched_shift); if (ii >= kp.n) break; i = (uint32_t)ii; }");
+        E.line("    else { if (j >= ex_count) break; i = ld_nt(kp.sched_pkts + ex_begin + j); }");
+        // this packet's descriptor, the next one's prefetch
+        if (lpf_on) emit_lpf_take();
+        else if (pf && xpf.on) emit_xpf_next();
+        else if (pf) emit_pf_next("pkt_next(kp, i, j + 1, ex_begin, ex_count)", "n_ != NO_PKT");
+        emit_kq();
+        if (ctx == CTX_SKB) emit_skb_load();
+        else emit_xdp_load();
+        emit_process_start(ctx == CTX_SKB ? nullptr : "P + L.M + 1", "    uint64_t r10 = kp.static_next + kp.frame_size;");
+        emit_entry_dispatch("kp.entry_prog");
+        emit_programs();
+        emit_result_stores("kq_", nullptr);
+        if (proc) emit_proc_store();
+        emit_loop_close();
+        if (vc_on) E.line("  VC_FLUSH();");
+        emit_kernel_close();
+    }
+    // Lane prefetch, at the lane's start: descriptors and windows of its first kLpfD packets into LDS.
+    void emit_lpf_park() {
+        const uint32_t D = kLpfD, XW = xpf.words;
+        E.line("  // lane prefetch: packets 0..%u of the lane, descriptors + P%u slot %u window (data + %u, %u words)", D - 1,
+               xpf.prog, xpf.hp, (uint32_t)xpf.off, XW);
+        E.line("  __shared__ uint64_t lpfo_[%uu * 256u];", D);
+        E.line("  __shared__ uint32_t lpfl_[%uu * 256u];", D);
+        E.line("  __shared__ uint64_t lpfw_[%uu * 256u];", D * XW);
+        E.line("  uint32_t lpf_n_ = 0u, xc_ok_ = 0u;");
+        E.line("  if (kp.entry_prog == %uu && !kp.headroom_arr && !kp.tailroom_arr && kp.headroom == 0u && kp.tailroom == 0u) {", xpf.prog);
+        for (uint32_t d = 0; d < D; d++) {
+            E.line("    const uint32_t lx%u_ = pkt_index(kp, g, %uu, ex_begin, ex_count);", d, d);
+            E.line("    uint64_t lo%u_ = 0; uint32_t ll%u_ = 0;", d, d);
+            E.line("    if (lx%u_ != NO_PKT) { lo%u_ = pkt_off_at(kp, lx%u_); ll%u_ = pkt_len_at(kp, lx%u_); }", d, d, d, d, d);
+        }
+        for (uint32_t d = 0; d < D; d++) {
+            for (uint32_t q = 0; q < XW; q++) E.line("    uint64_t lw%u_%u_ = 0;", d, q);
+            E.line("    const bool lk%u_ = lx%u_ != NO_PKT && %uu <= ll%u_;", d, d, (uint32_t)xpf.off + 8 * XW, d);
+            E.line("    if (lk%u_) {", d);
+            E.line("      const uint8_t *xp_ = kp.pkt_data + lo%u_ + %uu;", d, (uint32_t)xpf.off);
+            for (uint32_t q = 0; q < XW; q++) E.line("      lw%u_%u_ = ld_n(xp_ + %uu, 8u);", d, q, 8 * q);
+            E.line("    }");
+        }
+        for (uint32_t d = 0; d < D; d++) {
+            E.line("    lpfo_[%uu * 256u + threadIdx.x] = lo%u_;", d, d);
+            E.line("    lpfl_[%uu * 256u + threadIdx.x] = ll%u_ | (lk%u_ ? 0x80000000u : 0u);", d, d, d);
+            for (uint32_t q = 0; q < XW; q++) E.line("    lpfw_[%uu * 256u + threadIdx.x] = lw%u_%u_;", d * XW + q, d, q);
+        }
+        E.line("    lpf_n_ = lx0_ == NO_PKT ? 0u : lx1_ == NO_PKT ? 1u : lx2_ == NO_PKT ? 2u : lx3_ == NO_PKT ? 3u : 4u;");
+        E.line("  }");
+        static_assert(kLpfD == 4, "the lpf_n_ line above");
+    }
+    // ... and per packet: the parked descriptor and window, or plain loads past the first kLpfD
+    void emit_lpf_take() {
+        E.line("    uint64_t poff_; uint32_t plen_;");
+        for (uint32_t q = 0; q < xpf.words; q++) E.line("    uint64_t xc%u_ = 0;", q);
+        E.line("    if (j < lpf_n_) {   // parked in LDS when the lane started");
+        E.line("      poff_ = lpfo_[j * 256u + threadIdx.x];");
+        E.line("      const uint32_t lw_ = lpfl_[j * 256u + threadIdx.x];");
+        E.line("      plen_ = lw_ & 0x7fffffffu;");
+        E.line("      xc_ok_ = lw_ >> 31;");
+        for (uint32_t q = 0; q < xpf.words; q++)
+            E.line("      if (xc_ok_) xc%u_ = lpfw_[(j * %uu + %uu) * 256u + threadIdx.x];", q, xpf.words, q);
+        E.line("    } else {");
+        E.line("      poff_ = pkt_off_at(kp, i); plen_ = pkt_len_at(kp, i); xc_ok_ = 0u;");
+        E.line("    }");
+    }
+    // Window prefetch: descriptors two packets ahead, the window one packet ahead (analyze_xpf).
+    void emit_xpf_first() {
+        E.line("  const bool xpf_on_ = kp.entry_prog == %uu && !kp.headroom_arr;   // P%u slot %u window, data + %u, %u words",
+               xpf.prog, xpf.prog, xpf.hp, (uint32_t)xpf.off, xpf.words);
+        E.line("  uint64_t noff_ = 0, noff2_ = 0; uint32_t nlen_ = 0, nlen2_ = 0, nidx_ = NO_PKT, nidx2_ = NO_PKT, xn_ok_ = 0u, xc_ok_ = 0u;");
+        for (uint32_t q = 0; q < xpf.words; q++) E.line("  uint64_t xn%u_ = 0;", q);
+        E.line("  nidx_ = pkt_index(kp, g, 0u, ex_begin, ex_count);");
+        E.line("  if (nidx_ != NO_PKT) { noff_ = pkt_off_at(kp, nidx_); nlen_ = pkt_len_at(kp, nidx_); }");
+        emit_xpf_issue("  ");
+        E.line("  nidx2_ = nidx_ != NO_PKT ? pkt_next(kp, nidx_, 1u, ex_begin, ex_count) : NO_PKT;");
+        E.line("  if (nidx2_ != NO_PKT) { noff2_ = pkt_off_at(kp, nidx2_); nlen2_ = pkt_len_at(kp, nidx2_); }");
+    }
+    void emit_xpf_next() {
+        E.line("    const uint64_t poff_ = noff_; const uint32_t plen_ = nlen_;");
+        E.line("    xc_ok_ = xn_ok_;");
+        for (uint32_t q = 0; q < xpf.words; q++) E.line("    const uint64_t xc%u_ = xn%u_;", q, q);
+        E.line("    noff_ = noff2_; nlen_ = nlen2_; nidx_ = nidx2_;");
+        emit_xpf_issue("    ");
+        E.line("    nidx2_ = nidx_ != NO_PKT ? pkt_next(kp, nidx_, j + 2u, ex_begin, ex_count) : NO_PKT;");
+        E.line("    if (nidx2_ != NO_PKT) { noff2_ = pkt_off_at(kp, nidx2_); nlen2_ = pkt_len_at(kp, nidx2_); }");
+    }
+
+    // ---- the table spread: block b runs packets [b * SPREAD_PPB, +SPREAD_PPB) of the batch ----
+    // (analyze_spread admits only the xdp context, inlined slow paths, no census, no tail or local calls:
+    // no sk_buff load, process state or lane value cache in this form or the owned one)
+    void emit_spread() {
+        emit_kernel_open("0xffffffffu");
+        emit_lane_open();
+        // Thread t runs the block's packets at t, t + 256, ... (consecutive threads, consecutive
+        // packets); each packet's vCPU comes from the schedule.  Fused increments add into the
+        // block's LDS table, one row per vCPU lane its packets map to, (lane - lane0) mod V: at most
+        // SPREAD_PPB rows.
+        E.line("  const uint32_t blo_ = blockIdx.x * SPREAD_PPB, bhi_ = blo_ + SPREAD_PPB < kp.n ? blo_ + SPREAD_PPB : kp.n;");
+        E.line("  const uint32_t lam0_ = spread_lane(kp, blo_);");
+        E.line("  const DMap SM_ = cget(kp.maps, SPREAD_MAP);");
+        E.line("#if SPREAD_ROWS");
+        E.line("  __shared__ spread_t sacc_[SPREAD_ROWS * SPREAD_ROWW];");
+        E.line("  for (uint32_t w_ = threadIdx.x; w_ < SPREAD_ROWS * SPREAD_ROWW; w_ += 256u) sacc_[w_] = 0;");
+        E.line("  __syncthreads();");
+        E.line("#endif");
+        E.line("  uint32_t srow_ = 0, sbase_ = 0;");
+        // the lane of the thread's next packet: interleaved schedules step it by 256 mod V
+        // (no division per packet), chunked ones divide
+        E.line("  const uint32_t lstep_ = 256u %% kp.cpu_lanes;");
+        E.line("  uint32_t lam_ = spread_lane(kp, blo_ + threadIdx.x);");
+        emit_locals();
+        if (pf) emit_pf_first("blo_ + threadIdx.x", "n_ < bhi_");
+        E.line("  for (uint32_t j = 0; j < SPREAD_PPB / 256u; j++) {");
+        E.line("    const uint32_t i = blo_ + j * 256u + threadIdx.x;");
+        E.line("    if (i >= bhi_) break;");
+        if (pf) emit_pf_next("i + 256u", "n_ < bhi_");
+        emit_kq();
+        // this packet's vCPU (the schedule's lane for it) and its row of the spread map
+        E.line("    { if (kp.sched == SCHED_CHUNKED) lam_ = i / kp.per_lane;");
+        E.line("      else if (j) { lam_ += lstep_; if (lam_ >= kp.cpu_lanes) lam_ -= kp.cpu_lanes; }");
+        E.line("      L.cpu = (int32_t)(kp.vcpu_begin + lam_);");
+        E.line("      srow_ = lam_ >= lam0_ ? lam_ - lam0_ : lam_ + kp.cpu_lanes - lam0_;");
+        E.line("      sbase_ = SM_.backing_addr + (uint32_t)L.cpu * SM_.addr_period; }");
+        emit_xdp_load();
+        emit_process_start("P + L.M + 1", "    uint64_t r10 = kp.static_next + kp.frame_size;");
+        emit_entry_dispatch("kp.entry_prog");
+        emit_programs();
+        emit_result_stores("kq_", nullptr);
+        emit_loop_close();
+        // the block's counters into the map: one agent-scope add per non-zero counter (a row's
+        // counters are contiguous in the arena, so consecutive threads add consecutive words)
+        E.line("#if SPREAD_ROWS");
+        E.line("  __syncthreads();");
+        // a table that covers every vCPU lane (V <= packets per block): the block writes it,
+        // rotated to absolute lanes, into its slice of kp.spread_part with plain stores, and
+        // mimic_spread_reduce_kernel adds the blocks' slices into the map (one agent-scope add per
+        // counter per group of blocks, not per block: the per-block adds were 43 % of the kernel)
+        E.line("  if (kp.spread_part && kp.cpu_lanes == SPREAD_ROWS) {");
+        E.line("    spread_t *pt_ = (spread_t *)kp.spread_part + (size_t)blockIdx.x * (SPREAD_ROWS * SPREAD_ROWW);");
+        E.line("    for (uint32_t w_ = threadIdx.x; w_ < SPREAD_ROWS * SPREAD_ROWW; w_ += 256u) {");
+        E.line("      const uint32_t r_ = w_ / SPREAD_ROWW, q_ = w_ - r_ * SPREAD_ROWW;");
+        E.line("      const uint32_t lr_ = lam0_ + r_ < SPREAD_ROWS ? lam0_ + r_ : lam0_ + r_ - SPREAD_ROWS;");
+        E.line("      pt_[lr_ * SPREAD_ROWW + q_] = sacc_[w_];");
+        E.line("    }");
+        E.line("  } else");
+        E.line("  for (uint32_t w_ = threadIdx.x; w_ < SPREAD_ROWS * SPREAD_ROWW; w_ += 256u) {");
+        E.line("    const spread_t v_ = sacc_[w_];");
+        E.line("    if (!v_) continue;");
+        E.line("    const uint32_t r_ = w_ / SPREAD_ROWW, q_ = w_ - r_ * SPREAD_ROWW;");
+        E.line("    const uint32_t lr_ = lam0_ + r_ < kp.cpu_lanes ? lam0_ + r_ : lam0_ + r_ - kp.cpu_lanes;");
+        E.line("    spread_t *d_ = (spread_t *)(kp.arena + SM_.dev_off + (size_t)(kp.vcpu_begin + lr_) * SM_.dev_stride) + q_;");
+        E.line("    __hip_atomic_fetch_add((GAS spread_t *)d_, v_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);");
+        E.line("  }");
+        E.line("#endif");
+        emit_kernel_close();
+    }
+
+    // ---- the owned form: block b runs every packet of vCPU lanes [b * R, b * R + R) ----
+    void emit_owned() {
+        emit_kernel_open("0xffffffffu");
+        emit_lane_open();
+        // R = 256 / P (P = packets per lane): thread t the j-th packet (j = t / R) of lane b * R + t % R, so
+        // a wave's lanes take consecutive lanes' j-th packets (consecutive descriptors, packets
+        // and results).  Fused increments add into the block's LDS table, one row per lane; the
+        // block then adds its rows into the map with plain read-modify-writes: no other block
+        // touches those vCPUs' rows in this launch.
+        // Q = KParams::own_q packets per thread: R = 256 Q / P lanes, thread t their packets j,
+        // j + P / Q, ... in order (the engine picks Q so that the launch about fills the chip once)
+        E.line("  const uint32_t oP_ = kp.per_lane, oQ_ = kp.own_q, oS_ = oP_ / oQ_, oR_ = 256u / oS_;");
+        E.line("  const uint32_t orow_ = threadIdx.x %% oR_, oj_ = threadIdx.x / oR_, olane_ = blockIdx.x * oR_ + orow_;");
+        E.line("  const uint32_t osh_ = olane_ >= kp.sched_shift ? olane_ - kp.sched_shift : olane_ + kp.cpu_lanes - kp.sched_shift;");
+        // the thread's k-th packet.  Interleaved: packet j = oj_ + k (P / Q) of its lane.  Chunked
+        // (a lane's packets are contiguous): the block's 256 Q packets in order, thread t taking
+        // t, t + 256, ... -- consecutive threads on consecutive packets, whose lane is i / P
+        E.line("#define OWN_IDX_I(k_) ((oj_ < oS_ && olane_ < kp.cpu_lanes && (uint64_t)(oj_ + (k_) * oS_) * kp.cpu_lanes + osh_ < kp.n) ? (uint32_t)((uint64_t)(oj_ + (k_) * oS_) * kp.cpu_lanes + osh_) : NO_PKT)");
+        E.line("#define OWN_IDX_C(k_) ((threadIdx.x + 256u * (k_) < oR_ * oP_ && (uint64_t)blockIdx.x * oR_ * oP_ + threadIdx.x + 256u * (k_) < kp.n) ? (uint32_t)((uint64_t)blockIdx.x * oR_ * oP_ + threadIdx.x + 256u * (k_)) : NO_PKT)");
+        E.line("#define OWN_IDX(k_) (kp.sched == SCHED_CHUNKED ? OWN_IDX_C(k_) : OWN_IDX_I(k_))");
+        E.line("  const uint32_t oi_ = OWN_IDX(0u);");
+        // (OWN_IDX is used for the thread's first packet only, oi_.)  What is uniform for the launch
+        // is read from the kernarg segment once.  A thread's next packet is its index + ostr_
+        // while that is below olim_: interleaved, the stride oS_ * cpu_lanes under n (a stride past 2^32
+        // saturates: index + 0xffffffff is never below n); chunked, 256 under the end of the
+        // block's packets -- OWN_IDX(k + 1) given that OWN_IDX(k) is a packet.
+        E.line("  const bool ochk_ = kp.sched == SCHED_CHUNKED;");
+        E.line("  const uint64_t ostr64_ = ochk_ ? 256ull : (uint64_t)oS_ * kp.cpu_lanes;");
+        E.line("  const uint64_t oend_ = (uint64_t)blockIdx.x * oR_ * oP_ + (uint32_t)(oR_ * oP_);");
+        // ofl_: the launch has per-packet context arrays (1) or rooms (2); a plain launch with no
+        // rooms (0) reads no room and no array per packet.  Bits 4 and 8, set per batch below: the
+        // batch has no pkt_off / no pkt_len (a uniform batch, runtime.h pkt_off_at).
+        E.line("  uint32_t ofl_ = __builtin_amdgcn_readfirstlane((kp.headroom_arr || kp.tailroom_arr || kp.ingress_arr || kp.rxq_arr || kp.egress_arr ? 1u : 0u) | (kp.headroom | kp.tailroom ? 2u : 0u));");
+        E.line("  uint32_t ocpu_ = kp.vcpu_begin + olane_, oep_ = kp.entry_prog, or10_ = kp.static_next + kp.frame_size;");
+        // (pinned: the compiler would otherwise sink these loads back to their uses in the loop)
+        E.line("  uint32_t ostr_ = ostr64_ < 0xffffffffull ? (uint32_t)ostr64_ : 0xffffffffu;");
+        E.line("  uint32_t olim_ = ochk_ && oend_ < kp.n ? (uint32_t)oend_ : kp.n;");
+        E.line("  asm volatile(\"\" : \"+s\"(ostr_), \"+s\"(olim_), \"+s\"(ofl_), \"+s\"(oep_), \"+s\"(or10_));");
+        E.line("  asm volatile(\"\" : \"+v\"(ocpu_));");
+        E.line("  uint32_t oin_ = (uint32_t)kp.ingress, orx_ = (uint32_t)kp.rxq, oeg_ = (uint32_t)kp.egress;");
+        E.line("  asm volatile(\"\" : \"+s\"(oin_), \"+s\"(orx_), \"+s\"(oeg_));");
+        // Here go the instruction-table words the programs use (own_k, own_h), which are known once
+        // the programs are out: the rest is written into an emitter of its own and joined at the end.
+        Emitter head;
+        std::swap(head, E);
+        E.line("  const DMap SM_ = cget(kp.maps, SPREAD_MAP);");
+        E.line("  __shared__ spread_t sacc_[SPREAD_ROWS * SPREAD_ROWW];");
+        E.line("  for (uint32_t w_ = threadIdx.x; w_ < SPREAD_ROWS * SPREAD_ROWW; w_ += 256u) sacc_[w_] = 0;");
+        // The launch's batch references in LDS (512 bytes): the result arrays' addresses, and the
+        // next batch's descriptor arrays at a batch boundary, are read from here where they are
+        // used -- the r0 / status / steps / err_pc pointers and their null tests then hold no SGPR
+        // across the packet loop, where SGPRs are what runs out
+        E.line("  __shared__ BatchRef obr_[MIMIC_MANY_MAX];");
+        E.line("  if (threadIdx.x < (kp.many_n ? kp.many_n : 1u)) obr_[threadIdx.x] = kp.many_n ? cget(kp.many, threadIdx.x) : BatchRef{kp.pkt_data, kp.pkt_off, kp.pkt_len, kp.r0, kp.status, kp.steps, kp.err_pc, kp.pkt_stride | (uint64_t)kp.pkt_len_all << 32};");
+        E.line("  __syncthreads();");
+        E.line("  uint32_t srow_ = orow_, sbase_ = 0;");
+        // the row words this thread adds into at the end, loaded now (their round trip overlaps
+        // the packet's): word threadIdx.x of the block's rows (R * SPREAD_ROWW <= 256 words)
+        E.line("  const bool ofw_ = threadIdx.x < oR_ * SPREAD_ROWW && blockIdx.x * oR_ + threadIdx.x / SPREAD_ROWW < kp.cpu_lanes;");
+        E.line("  GAS spread_t *const ofd_ = (GAS spread_t *)(kp.arena + SM_.dev_off + (size_t)(kp.vcpu_begin + blockIdx.x * oR_ + threadIdx.x / SPREAD_ROWW) * SM_.dev_stride) + threadIdx.x %% SPREAD_ROWW;");
+        E.line("  const spread_t ofv_ = ofw_ ? *ofd_ : (spread_t)0;");
+        emit_locals();
+        // Multi-batch launches (mimic_run_xdp_many): every thread runs its packets of batch 0, then
+        // of batch 1, ... (all batches have the same n, so the same packet indices), the block's
+        // LDS counter table accumulating over all of them and flushed once; the last packet of a
+        // batch prefetches the next batch's first descriptor.  many_n = 0: the one batch in kp.
+        // The descriptor of the running packet lives in poff_ / plen_ across iterations: the
+        // prefetched one (noff_ / nlen_) is moved there at the end of the packet before, ahead of
+        // its result stores, so the next packet's first loads wait for nothing.
+        if (pf) E.line("  uint64_t noff_ = 0, poff_ = 0; uint32_t nlen_ = 0, plen_ = 0;");
+        E.line("  const uint32_t nb_ = kp.many_n ? kp.many_n : 1u;");
+        E.line("  bool bpre_ = false;   // this batch's first descriptor came with the previous batch's last packet");
+        E.line("  for (uint32_t bt_ = 0; bt_ < nb_; bt_++) {");
+        E.line("  const BatchRef br_ = kp.many_n ? cget(kp.many, bt_) : BatchRef{kp.pkt_data, kp.pkt_off, kp.pkt_len, kp.r0, kp.status, kp.steps, kp.err_pc, kp.pkt_stride | (uint64_t)kp.pkt_len_all << 32};");
+        // A uniform batch (null pkt_off / pkt_len) issues no descriptor load: the offset is the
+        // packet's index times the batch's stride, the length its one length.  The two scalars
+        // live in VGPRs (the loop has those to spare, not SGPRs: DESIGN 6.2); which form the batch
+        // has goes into ofl_ (4: no pkt_off, 8: no pkt_len), and the packet loop tests a copy pinned
+        // per packet (a hoisted test would hold a lane mask, two SGPRs, across the loop).
+        E.line("  uint32_t cstr_ = (uint32_t)br_.compact, clen_ = (uint32_t)(br_.compact >> 32);");
+        E.line("  asm volatile(\"\" : \"+v\"(cstr_), \"+v\"(clen_));");
+        E.line("  ofl_ = (ofl_ & 3u) | (br_.pkt_off ? 0u : 4u) | (br_.pkt_len ? 0u : 8u);");
+        if (pf) {   // the batch's first descriptor: computed, or prefetched by the batch before, or loaded now
+            E.line("  if (oi_ != NO_PKT) {");
+            E.line("    if (!bpre_) { pkt_off_pf(!(ofl_ & 4u), br_.pkt_off, oi_, noff_); pkt_len_pf(!(ofl_ & 8u), br_.pkt_len, oi_, nlen_); }");
+            E.line("    poff_ = pkt_off_take(!(ofl_ & 4u), noff_, cstr_, oi_); plen_ = pkt_len_take(!(ofl_ & 8u), nlen_, clen_);");
+            E.line("  }");
+            E.line("  bpre_ = false;");
+        }
+        E.line("  uint32_t oni_ = oi_;   // the thread's next packet");
+        E.line("  for (uint32_t j = 0; j < oQ_; j++) {   // the thread's packets of its lane, in order");
+        E.line("    const uint32_t i = oni_;");
+        E.line("    if (i == NO_PKT) break;");
+        E.line("    oni_ = NO_PKT;");
+        E.line("    if (j + 1u < oQ_) { const uint64_t x_ = (uint64_t)i + ostr_; if (x_ < olim_) oni_ = (uint32_t)x_; }");
+        if (pf) {
+            // (a uniform batch prefetches nothing: its next descriptor is computed at L_term; at a
+            // batch boundary the next batch's form decides, read with its arrays from LDS)
+            E.line("    uint32_t cf_ = ofl_; asm volatile(\"\" : \"+s\"(cf_));");
+            // One load site and one mask for both cases, as before: the two addresses are chosen
+            // first, and both loads are made when the batch has either array.  An array the batch
+            // does not have (one of the two only) is read from the kernarg segment instead, 8 valid
+            // bytes whose value pkt_*_take never looks at.
+            E.line("    const uint64_t *po_ = nullptr; const uint32_t *pl_ = nullptr;");
+            E.line("    if (j + 1u < oQ_) { if (oni_ != NO_PKT && (cf_ & 12u) != 12u) { po_ = (cf_ & 4u) ? (const uint64_t *)&kp : br_.pkt_off + oni_; pl_ = (cf_ & 8u) ? (const uint32_t *)&kp : br_.pkt_len + oni_; } }");
+            E.line("    else if (bt_ + 1u < nb_ && oi_ != NO_PKT) { const BatchRef &nx_ = obr_[bt_ + 1u];");
+            E.line("      if (nx_.pkt_off || nx_.pkt_len) { po_ = nx_.pkt_off ? nx_.pkt_off + oi_ : (const uint64_t *)&kp; pl_ = nx_.pkt_len ? nx_.pkt_len + oi_ : (const uint32_t *)&kp; }");
+            E.line("      bpre_ = true; }");
+            E.line("    if (po_) { pkt_off_pf(true, po_, 0u, noff_); pkt_len_pf(true, pl_, 0u, nlen_); }");
+        }
+        emit_kq();
+        // the packet's vCPU and its row of the spread map (chunked: per packet)
+        E.line("    { const uint32_t ol_ = ochk_ ? i / oP_ : olane_;");
+        E.line("      srow_ = ol_ - blockIdx.x * oR_;");
+        E.line("      L.cpu = (int32_t)(ocpu_ - olane_ + ol_);");
+        E.line("      sbase_ = SM_.backing_addr + (uint32_t)L.cpu * SM_.addr_period; }");
+        // NewProcess + LinuxContextXDP.Load; a plain launch (ofl_ = 0): no room, no array, only the
+        // interface scalars (and no rooms to zero)
+        E.line("    uint32_t H = 0u, T = 0u;");
+        E.line("    L.ingress = oin_; L.rxq = orx_; L.egress = oeg_;");
+        E.line("    if (ofl_ & 3u) {");
+        E.line("      H = kq_.headroom_arr ? ld_nt(kq_.headroom_arr + i) : kq_.headroom;");
+        E.line("      T = kq_.tailroom_arr ? ld_nt(kq_.tailroom_arr + i) : kq_.tailroom;");
+        E.line("      if (kq_.ingress_arr) L.ingress = (uint32_t)ld_nt(kq_.ingress_arr + i);");
+        E.line("      if (kq_.rxq_arr) L.rxq = (uint32_t)ld_nt(kq_.rxq_arr + i);");
+        E.line("      if (kq_.egress_arr) L.egress = (uint32_t)ld_nt(kq_.egress_arr + i);");
+        E.line("    }");
+        emit_xdp_extent("br_.pkt_data", "pkt_len_at(!(ofl_ & 8u), br_.pkt_len, clen_, i)",
+                        "pkt_off_at(!(ofl_ & 4u), br_.pkt_off, cstr_, i)", "if (ofl_ & 3u)");
+        // (the r10 copy is pinned again per packet: the stack arithmetic of the cold paths would
+        // otherwise be hoisted out of the loop, one live SGPR per derived value)
+        emit_process_start("P + L.M + 1", "    uint32_t lr10_ = or10_; asm volatile(\"\" : \"+s\"(lr10_));\n    uint64_t r10 = lr10_;");
+        emit_entry_dispatch("oep_");
+        emit_programs();
+        // the next packet's descriptor is taken here, ahead of the result stores: the
+        // wait for it (it came back with this packet's first loads) is the last one before the next
+        // packet's window loads, which the stores' acknowledgements then travel with
+        // (a uniform batch: index * stride and the one length instead; after a batch's last packet the
+        // next batch's top sets both)
+        // (the form bits pinned again here: a copy held from the loop top would be one more live SGPR)
+        if (pf) E.line("    { uint32_t ct_ = ofl_; asm volatile(\"\" : \"+s\"(ct_)); poff_ = pkt_off_take(!(ct_ & 4u), noff_, cstr_, oni_); plen_ = pkt_len_take(!(ct_ & 8u), nlen_, clen_); asm volatile(\"\" : \"+v\"(poff_), \"+v\"(plen_)); }");
+        // the results go to the batch of this iteration, its addresses read from the block's LDS copy
+        // of the batch references (obr_): no SGPR holds them across the loop
+        // (by reference: each address is read just ahead of its store)
+        emit_result_stores("lb_", "    const BatchRef &lb_ = obr_[bt_];");
+        emit_loop_close();
+        E.line("  }   // batches");
+        // the block's rows into the map: plain read-modify-writes (the block owns these vCPUs)
+        E.line("  __syncthreads();");
+        E.line("  if (ofw_ && sacc_[threadIdx.x]) *ofd_ = ofv_ + sacc_[threadIdx.x];");
+        E.line("  for (uint32_t w_ = threadIdx.x + 256u; w_ < oR_ * SPREAD_ROWW; w_ += 256u) {   // rows past 256 words");
+        E.line("    const spread_t v_ = sacc_[w_];");
+        E.line("    if (!v_) continue;");
+        E.line("    const uint32_t r_ = w_ / SPREAD_ROWW, q_ = w_ - r_ * SPREAD_ROWW;");
+        E.line("    GAS spread_t *d_ = (GAS spread_t *)(kp.arena + SM_.dev_off + (size_t)(kp.vcpu_begin + blockIdx.x * oR_ + r_) * SM_.dev_stride) + q_;");
+        E.line("    *d_ += v_;");
+        E.line("  }");
+        emit_kernel_close();
+        // own_hoist: an LD_IMM64 slot's constant (own_k), its map hint (own_h) -- only the half that
+        // is used -- read once ahead of the batch loop and pinned in SGPRs
+        for (uint32_t s : own_k) head.line("  uint64_t hk%u_ = cget(kp.insns, %uu).k; asm volatile(\"\" : \"+s\"(hk%u_));", s, s, s);
+        for (uint32_t s : own_h) head.line("  uint32_t hh%u_ = AUX_MAPHINT(cget(kp.insns, %uu).aux); asm volatile(\"\" : \"+s\"(hh%u_));", s, s, s);
+        if (own_k.empty() && own_h.empty()) head.s += '\n';
+        E.s = head.s + E.s;
+    }
+
+    // ---- pieces that are the same text in more than one form; the arguments are the strings that differ ----
+    // signature to the block-wide initialisations (chunk_lanes: the lanes h_chunk_init counts waves over)
+    void emit_kernel_open(const char *chunk_lanes) {
         E.line("extern \"C\" __global__ __launch_bounds__(256) %svoid mimic_jit_kernel(const KParams kp_arg_) {",
-               wv > 0 ? ("__attribute__((amdgpu_waves_per_eu(" + std::to_string(wv) + "))) ").c_str() : "");
+               waves_attr > 0 ? ("__attribute__((amdgpu_waves_per_eu(" + std::to_string(waves_attr) + "))) ").c_str() : "");
         // the parameters stay in the kernarg segment (constant address space): an opaque
         // constant-space pointer keeps every field a scalar load where it is used (not all
         // preloaded into SGPRs at entry)
@@ -372,114 +745,38 @@ class Gen {
         E.line("  const KParams *kpp = (const KParams *)kp4_;");
         E.line("  const KParams &kp = *kpp;");
         E.line("  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;");
-        if (hash_chunk) E.line("  h_chunk_init(%s);   // (its waves: those the early return below keeps)", spread_on ? "0xffffffffu" : "kp.lanes");
+        if (hash_chunk) E.line("  h_chunk_init(%s);   // (its waves: those the early return below keeps)", chunk_lanes);
         if (hash_combine) E.line("  h_comb_init();   // before any thread of the block can leave");
-        if (!spread_on) E.line("  if (g >= kp.lanes) return;");
-        skb_lds = ctx == CTX_SKB && fast_paths && skb_fields && skb_lds_knob;
+    }
+    void emit_lane_open() {
         // the sk_buff records of the block's lanes, 168 bytes apart (an odd number of 8-byte
         // words: lanes reading the same field hit different banks); nothing reads them back
         if (skb_lds) E.line("  __shared__ uint64_t srec_[%uu * 256u];", kSrecQ);
         E.line("  Lane L;");
         E.line("  Spill sp_;");
-        if (census) {
+        if (census) {   // diagnostics: each slow-path call adds 1 to its kind's 4-bit field of coldn_ (cold())
             E.line("  uint32_t coldn_ = 0;");
             E.line("#define COLD_CALL_K(k_, call_, pc_) do { coldn_ += 1u << (k_); COLD_CALL(call_, pc_); } while (0)");
         }
         E.line("  L.lane = g;");
-        if (spread_own) {
-            // Owned spread: block b runs every packet of vCPU lanes [b * R, b * R + R), R = 256 / P
-            // (P = packets per lane): thread t the j-th packet (j = t / R) of lane b * R + t % R, so
-            // a wave's lanes take consecutive lanes' j-th packets (consecutive descriptors, packets
-            // and results).  Fused increments add into the block's LDS table, one row per lane; the
-            // block then adds its rows into the map with plain read-modify-writes: no other block
-            // touches those vCPUs' rows in this launch.
-            // Q = KParams::own_q packets per thread: R = 256 Q / P lanes, thread t their packets j,
-            // j + P / Q, ... in order (the engine picks Q so that the launch about fills the chip once)
-            E.line("  const uint32_t oP_ = kp.per_lane, oQ_ = kp.own_q, oS_ = oP_ / oQ_, oR_ = 256u / oS_;");
-            E.line("  const uint32_t orow_ = threadIdx.x %% oR_, oj_ = threadIdx.x / oR_, olane_ = blockIdx.x * oR_ + orow_;");
-            E.line("  const uint32_t osh_ = olane_ >= kp.sched_shift ? olane_ - kp.sched_shift : olane_ + kp.cpu_lanes - kp.sched_shift;");
-            // the thread's k-th packet.  Interleaved: packet j = oj_ + k (P / Q) of its lane.  Chunked
-            // (a lane's packets are contiguous): the block's 256 Q packets in order, thread t taking
-            // t, t + 256, ... -- consecutive threads on consecutive packets, whose lane is i / P
-            E.line("#define OWN_IDX_I(k_) ((oj_ < oS_ && olane_ < kp.cpu_lanes && (uint64_t)(oj_ + (k_) * oS_) * kp.cpu_lanes + osh_ < kp.n) ? (uint32_t)((uint64_t)(oj_ + (k_) * oS_) * kp.cpu_lanes + osh_) : NO_PKT)");
-            E.line("#define OWN_IDX_C(k_) ((threadIdx.x + 256u * (k_) < oR_ * oP_ && (uint64_t)blockIdx.x * oR_ * oP_ + threadIdx.x + 256u * (k_) < kp.n) ? (uint32_t)((uint64_t)blockIdx.x * oR_ * oP_ + threadIdx.x + 256u * (k_)) : NO_PKT)");
-            E.line("#define OWN_IDX(k_) (kp.sched == SCHED_CHUNKED ? OWN_IDX_C(k_) : OWN_IDX_I(k_))");
-            E.line("  const uint32_t oi_ = OWN_IDX(0u);");
-            // (OWN_IDX is used for the thread's first packet only, oi_.)  What is uniform for the launch
-            // is read from the kernarg segment once.  A thread's next packet is its index + ostr_
-            // while that is below olim_: interleaved, the stride oS_ * cpu_lanes under n (a stride past 2^32
-            // saturates: index + 0xffffffff is never below n); chunked, 256 under the end of the
-            // block's packets -- OWN_IDX(k + 1) given that OWN_IDX(k) is a packet.
-            E.line("  const bool ochk_ = kp.sched == SCHED_CHUNKED;");
-            E.line("  const uint64_t ostr64_ = ochk_ ? 256ull : (uint64_t)oS_ * kp.cpu_lanes;");
-            E.line("  const uint64_t oend_ = (uint64_t)blockIdx.x * oR_ * oP_ + (uint32_t)(oR_ * oP_);");
-            // ofl_: the launch has per-packet context arrays (1) or rooms (2); a plain launch with no
-            // rooms (0) reads no room and no array per packet.  Bits 4 and 8, set per batch below: the
-            // batch has no pkt_off / no pkt_len (a uniform batch, runtime.h pkt_off_at).
-            E.line("  uint32_t ofl_ = __builtin_amdgcn_readfirstlane((kp.headroom_arr || kp.tailroom_arr || kp.ingress_arr || kp.rxq_arr || kp.egress_arr ? 1u : 0u) | (kp.headroom | kp.tailroom ? 2u : 0u));");
-            E.line("  uint32_t ocpu_ = kp.vcpu_begin + olane_, oep_ = kp.entry_prog, or10_ = kp.static_next + kp.frame_size;");
-            // (pinned: the compiler would otherwise sink these loads back to their uses in the loop)
-            E.line("  uint32_t ostr_ = ostr64_ < 0xffffffffull ? (uint32_t)ostr64_ : 0xffffffffu;");
-            E.line("  uint32_t olim_ = ochk_ && oend_ < kp.n ? (uint32_t)oend_ : kp.n;");
-            E.line("  asm volatile(\"\" : \"+s\"(ostr_), \"+s\"(olim_), \"+s\"(ofl_), \"+s\"(oep_), \"+s\"(or10_));");
-            E.line("  asm volatile(\"\" : \"+v\"(ocpu_));");
-            E.line("  uint32_t oin_ = (uint32_t)kp.ingress, orx_ = (uint32_t)kp.rxq, oeg_ = (uint32_t)kp.egress;");
-            E.line("  asm volatile(\"\" : \"+s\"(oin_), \"+s\"(orx_), \"+s\"(oeg_));");
-            E.line("%s", kOwnHoist);   // the instruction-table words the programs use (own_hoist)
-            E.line("  const DMap SM_ = cget(kp.maps, SPREAD_MAP);");
-            E.line("  __shared__ spread_t sacc_[SPREAD_ROWS * SPREAD_ROWW];");
-            E.line("  for (uint32_t w_ = threadIdx.x; w_ < SPREAD_ROWS * SPREAD_ROWW; w_ += 256u) sacc_[w_] = 0;");
-            // The launch's batch references in LDS (512 bytes): the result arrays' addresses, and the
-            // next batch's descriptor arrays at a batch boundary, are read from here where they are
-            // used -- the r0 / status / steps / err_pc pointers and their null tests then hold no SGPR
-            // across the packet loop, where SGPRs are what runs out
-            E.line("  __shared__ BatchRef obr_[MIMIC_MANY_MAX];");
-            E.line("  if (threadIdx.x < (kp.many_n ? kp.many_n : 1u)) obr_[threadIdx.x] = kp.many_n ? cget(kp.many, threadIdx.x) : BatchRef{kp.pkt_data, kp.pkt_off, kp.pkt_len, kp.r0, kp.status, kp.steps, kp.err_pc, kp.pkt_stride | (uint64_t)kp.pkt_len_all << 32};");
-            E.line("  __syncthreads();");
-            E.line("  uint32_t srow_ = orow_, sbase_ = 0;");
-            // the row words this thread adds into at the end, loaded now (their round trip overlaps
-            // the packet's): word threadIdx.x of the block's rows (R * SPREAD_ROWW <= 256 words)
-            E.line("  const bool ofw_ = threadIdx.x < oR_ * SPREAD_ROWW && blockIdx.x * oR_ + threadIdx.x / SPREAD_ROWW < kp.cpu_lanes;");
-            E.line("  GAS spread_t *const ofd_ = (GAS spread_t *)(kp.arena + SM_.dev_off + (size_t)(kp.vcpu_begin + blockIdx.x * oR_ + threadIdx.x / SPREAD_ROWW) * SM_.dev_stride) + threadIdx.x %% SPREAD_ROWW;");
-            E.line("  const spread_t ofv_ = ofw_ ? *ofd_ : (spread_t)0;");
-        } else if (spread_on) {
-            // Spread: block b runs packets [b * SPREAD_PPB, +SPREAD_PPB) of the batch, thread t the
-            // ones at t, t + 256, ... (consecutive threads, consecutive packets); each packet's
-            // vCPU comes from the schedule.  Fused increments add into the block's LDS table, one
-            // row per vCPU lane its packets map to, (lane - lane0) mod V: at most SPREAD_PPB rows.
-            E.line("  const uint32_t blo_ = blockIdx.x * SPREAD_PPB, bhi_ = blo_ + SPREAD_PPB < kp.n ? blo_ + SPREAD_PPB : kp.n;");
-            E.line("  const uint32_t lam0_ = spread_lane(kp, blo_);");
-            E.line("  const DMap SM_ = cget(kp.maps, SPREAD_MAP);");
-            E.line("#if SPREAD_ROWS");
-            E.line("  __shared__ spread_t sacc_[SPREAD_ROWS * SPREAD_ROWW];");
-            E.line("  for (uint32_t w_ = threadIdx.x; w_ < SPREAD_ROWS * SPREAD_ROWW; w_ += 256u) sacc_[w_] = 0;");
-            E.line("  __syncthreads();");
-            E.line("#endif");
-            E.line("  uint32_t srow_ = 0, sbase_ = 0;");
-            // the lane of the thread's next packet: interleaved schedules step it by 256 mod V
-            // (no division per packet), chunked ones divide
-            E.line("  const uint32_t lstep_ = 256u %% kp.cpu_lanes;");
-            E.line("  uint32_t lam_ = spread_lane(kp, blo_ + threadIdx.x);");
+    }
+    // the lane's own row of the per-CPU array the hint names (analyze_vc)
+    void emit_vc_open() {
+        if (vc_lds) {
+            // rows over 32 bytes: the lane's row in its LDS slot, dword d at lvc_[d * 256 + thread]
+            // (two spare dwords: an unaligned read at the row's end stays in the array)
+            E.line("  __shared__ uint32_t lvc_[(%uu / 4u + 2u) * 256u];", vc_rb);
+            E.line("  uint32_t *const lvt_ = lvc_ + threadIdx.x;");
+            E.line("  constexpr uint32_t vcb_ = %uu;   // the row's bytes", vc_rb);
+            E.line("  uint32_t vcv_ = 0u, vcd_ = 0u, vclo_ = 0u; uint8_t *vcp_ = nullptr;");
         } else {
-            E.line("  L.cpu = lane_cpu(kp, g);");
+            E.line("  uint64_t vc0_ = 0, vc1_ = 0, vc2_ = 0, vc3_ = 0; uint32_t vcv_ = 0u, vcd_ = 0u, vclo_ = 0u, vcb_ = 0u; uint8_t *vcp_ = nullptr;");
         }
-        if (vc_on) {
-            // the lane's own row of the per-CPU array the hint names (analyze_vc)
-            if (vc_lds) {
-                // rows over 32 bytes: the lane's row in its LDS slot, dword d at lvc_[d * 256 + thread]
-                // (two spare dwords: an unaligned read at the row's end stays in the array)
-                E.line("  __shared__ uint32_t lvc_[(%uu / 4u + 2u) * 256u];", vc_rb);
-                E.line("  uint32_t *const lvt_ = lvc_ + threadIdx.x;");
-                E.line("  constexpr uint32_t vcb_ = %uu;   // the row's bytes", vc_rb);
-                E.line("  uint32_t vcv_ = 0u, vcd_ = 0u, vclo_ = 0u; uint8_t *vcp_ = nullptr;");
-                E.line("  { const uint32_t mh_ = AUX_MAPHINT(cget(kp.insns, %uu).aux);", vc_slot);
-                E.line("    if (mh_) lvc_open(kp, cget(kp.maps, mh_ - 1u), L.cpu, vcb_, vcp_, vclo_, vcv_, lvt_); }");
-            } else {
-                E.line("  uint64_t vc0_ = 0, vc1_ = 0, vc2_ = 0, vc3_ = 0; uint32_t vcv_ = 0u, vcd_ = 0u, vclo_ = 0u, vcb_ = 0u; uint8_t *vcp_ = nullptr;");
-                E.line("  { const uint32_t mh_ = AUX_MAPHINT(cget(kp.insns, %uu).aux);", vc_slot);
-                E.line("    if (mh_) vc_open(kp, cget(kp.maps, mh_ - 1u), L.cpu, vcp_, vclo_, vcb_, vcv_, vc0_, vc1_, vc2_, vc3_); }");
-            }
-        }
+        E.line("  { const uint32_t mh_ = AUX_MAPHINT(cget(kp.insns, %uu).aux);", vc_slot);
+        if (vc_lds) E.line("    if (mh_) lvc_open(kp, cget(kp.maps, mh_ - 1u), L.cpu, vcb_, vcp_, vclo_, vcv_, lvt_); }");
+        else E.line("    if (mh_) vc_open(kp, cget(kp.maps, mh_ - 1u), L.cpu, vcp_, vclo_, vcb_, vcv_, vc0_, vc1_, vc2_, vc3_); }");
+    }
+    void emit_locals() {
         E.line("  uint32_t ex_begin = 0, ex_count = 0;");
         E.line("  if (kp.sched == SCHED_EXPLICIT) { ex_begin = *gp(kp.sched_start + g); ex_count = *gp(kp.sched_start + g + 1) - ex_begin; }");
         E.line("  uint64_t lane_steps = 0;");
@@ -492,222 +789,58 @@ class Gen {
             E.line("  %s sp%u_%u_ = 0;   // packet load of P%u slot %u, issued early", u.second == 8 ? "uint64_t" : "uint32_t",
                    u.first.first, u.first.second, u.first.first, u.first.second);
         if (!spec_use.empty()) E.line("  uint32_t spv_ = 1;   // 0 once a store through R10 left the stack: early values void");
-        // The packet loop is software-pipelined by one descriptor: packet j+1's index, offset and
-        // length are loaded while packet j runs (they travel with packet j's first loads), which
-        // takes one dependent HBM round trip off every packet after the first.
-        const bool pf = ctx == CTX_XDP && prefetch;
-        if (!spec_use.empty() && !spread_on) analyze_xpf();
-        // (LDS budget: 4 blocks of 256 lanes per CU with the window alone; no other LDS user)
-        lpf_on = pf && xpf.on && lpf_knob && !xpf_knob && !spread_on && !vc_lds && !lds_stack_on && !defer_mode &&
-                 !hash_combine && lpf_safe();
-        if (!lpf_on && !xpf_knob) xpf.on = false;   // (the one-packet-ahead form only on request)
-        if (spread_own) {
-            // Multi-batch launches (mimic_run_xdp_many): every thread runs its packets of batch 0, then
-            // of batch 1, ... (all batches have the same n, so the same packet indices), the block's
-            // LDS counter table accumulating over all of them and flushed once; the last packet of a
-            // batch prefetches the next batch's first descriptor.  many_n = 0: the one batch in kp.
-            // The descriptor of the running packet lives in poff_ / plen_ across iterations: the
-            // prefetched one (noff_ / nlen_) is moved there at the end of the packet before, ahead of
-            // its result stores, so the next packet's first loads wait for nothing.
-            if (pf) E.line("  uint64_t noff_ = 0, poff_ = 0; uint32_t nlen_ = 0, plen_ = 0;");
-            E.line("  const uint32_t nb_ = kp.many_n ? kp.many_n : 1u;");
-            E.line("  bool bpre_ = false;   // this batch's first descriptor came with the previous batch's last packet");
-            E.line("  for (uint32_t bt_ = 0; bt_ < nb_; bt_++) {");
-            E.line("  const BatchRef br_ = kp.many_n ? cget(kp.many, bt_) : BatchRef{kp.pkt_data, kp.pkt_off, kp.pkt_len, kp.r0, kp.status, kp.steps, kp.err_pc, kp.pkt_stride | (uint64_t)kp.pkt_len_all << 32};");
-            // A uniform batch (null pkt_off / pkt_len) issues no descriptor load: the offset is the
-            // packet's index times the batch's stride, the length its one length.  The two scalars
-            // live in VGPRs (the loop has those to spare, not SGPRs: DESIGN 6.2); which form the batch
-            // has goes into ofl_ (4: no pkt_off, 8: no pkt_len), and the packet loop tests a copy pinned
-            // per packet (a hoisted test would hold a lane mask, two SGPRs, across the loop).
-            E.line("  uint32_t cstr_ = (uint32_t)br_.compact, clen_ = (uint32_t)(br_.compact >> 32);");
-            E.line("  asm volatile(\"\" : \"+v\"(cstr_), \"+v\"(clen_));");
-            E.line("  ofl_ = (ofl_ & 3u) | (br_.pkt_off ? 0u : 4u) | (br_.pkt_len ? 0u : 8u);");
-        }
-        if (lpf_on) {
-            const uint32_t D = kLpfD, XW = xpf.words;
-            E.line("  // lane prefetch: packets 0..%u of the lane, descriptors + P%u slot %u window (data + %u, %u words)", D - 1,
-                   xpf.prog, xpf.hp, (uint32_t)xpf.off, XW);
-            E.line("  __shared__ uint64_t lpfo_[%uu * 256u];", D);
-            E.line("  __shared__ uint32_t lpfl_[%uu * 256u];", D);
-            E.line("  __shared__ uint64_t lpfw_[%uu * 256u];", D * XW);
-            E.line("  uint32_t lpf_n_ = 0u, xc_ok_ = 0u;");
-            E.line("  if (kp.entry_prog == %uu && !kp.headroom_arr && !kp.tailroom_arr && kp.headroom == 0u && kp.tailroom == 0u) {", xpf.prog);
-            for (uint32_t d = 0; d < D; d++) {
-                E.line("    const uint32_t lx%u_ = pkt_index(kp, g, %uu, ex_begin, ex_count);", d, d);
-                E.line("    uint64_t lo%u_ = 0; uint32_t ll%u_ = 0;", d, d);
-                E.line("    if (lx%u_ != NO_PKT) { lo%u_ = pkt_off_at(kp, lx%u_); ll%u_ = pkt_len_at(kp, lx%u_); }", d, d, d, d, d);
-            }
-            for (uint32_t d = 0; d < D; d++) {
-                for (uint32_t q = 0; q < XW; q++) E.line("    uint64_t lw%u_%u_ = 0;", d, q);
-                E.line("    const bool lk%u_ = lx%u_ != NO_PKT && %uu <= ll%u_;", d, d, (uint32_t)xpf.off + 8 * XW, d);
-                E.line("    if (lk%u_) {", d);
-                E.line("      const uint8_t *xp_ = kp.pkt_data + lo%u_ + %uu;", d, (uint32_t)xpf.off);
-                for (uint32_t q = 0; q < XW; q++) E.line("      lw%u_%u_ = ld_n(xp_ + %uu, 8u);", d, q, 8 * q);
-                E.line("    }");
-            }
-            for (uint32_t d = 0; d < D; d++) {
-                E.line("    lpfo_[%uu * 256u + threadIdx.x] = lo%u_;", d, d);
-                E.line("    lpfl_[%uu * 256u + threadIdx.x] = ll%u_ | (lk%u_ ? 0x80000000u : 0u);", d, d, d);
-                for (uint32_t q = 0; q < XW; q++) E.line("    lpfw_[%uu * 256u + threadIdx.x] = lw%u_%u_;", d * XW + q, d, q);
-            }
-            E.line("    lpf_n_ = lx0_ == NO_PKT ? 0u : lx1_ == NO_PKT ? 1u : lx2_ == NO_PKT ? 2u : lx3_ == NO_PKT ? 3u : 4u;");
-            E.line("  }");
-            static_assert(kLpfD == 4, "the lpf_n_ line above");
-        } else if (pf && xpf.on) {
-            // descriptors two packets ahead, the window one packet ahead (analyze_xpf)
-            E.line("  const bool xpf_on_ = kp.entry_prog == %uu && !kp.headroom_arr;   // P%u slot %u window, data + %u, %u words",
-                   xpf.prog, xpf.prog, xpf.hp, (uint32_t)xpf.off, xpf.words);
-            E.line("  uint64_t noff_ = 0, noff2_ = 0; uint32_t nlen_ = 0, nlen2_ = 0, nidx_ = NO_PKT, nidx2_ = NO_PKT, xn_ok_ = 0u, xc_ok_ = 0u;");
-            for (uint32_t q = 0; q < xpf.words; q++) E.line("  uint64_t xn%u_ = 0;", q);
-            E.line("  nidx_ = pkt_index(kp, g, 0u, ex_begin, ex_count);");
-            E.line("  if (nidx_ != NO_PKT) { noff_ = pkt_off_at(kp, nidx_); nlen_ = pkt_len_at(kp, nidx_); }");
-            emit_xpf_issue("  ");
-            E.line("  nidx2_ = nidx_ != NO_PKT ? pkt_next(kp, nidx_, 1u, ex_begin, ex_count) : NO_PKT;");
-            E.line("  if (nidx2_ != NO_PKT) { noff2_ = pkt_off_at(kp, nidx2_); nlen2_ = pkt_len_at(kp, nidx2_); }");
-        } else if (pf) {
-            if (spread_own)
-            {   // the batch's first descriptor: computed, or prefetched by the batch before, or loaded now
-                E.line("  if (oi_ != NO_PKT) {");
-                E.line("    if (!bpre_) { pkt_off_pf(!(ofl_ & 4u), br_.pkt_off, oi_, noff_); pkt_len_pf(!(ofl_ & 8u), br_.pkt_len, oi_, nlen_); }");
-                E.line("    poff_ = pkt_off_take(!(ofl_ & 4u), noff_, cstr_, oi_); plen_ = pkt_len_take(!(ofl_ & 8u), nlen_, clen_);");
-                E.line("  }");
-                E.line("  bpre_ = false;");
-            }
-            else
-                E.line("  uint64_t noff_ = 0; uint32_t nlen_ = 0;");
-            if (spread_own) {
-            } else if (spread_on)
-                E.line("  { const uint32_t n_ = blo_ + threadIdx.x; if (n_ < bhi_) pkt_desc_pf(kp, n_, noff_, nlen_); }");
-            else
-                E.line("  { const uint32_t n_ = pkt_index(kp, g, 0u, ex_begin, ex_count); if (n_ != NO_PKT) pkt_desc_pf(kp, n_, noff_, nlen_); }");
-        }
-        if (spread_own) {
-            E.line("  uint32_t oni_ = oi_;   // the thread's next packet");
-            E.line("  for (uint32_t j = 0; j < oQ_; j++) {   // the thread's packets of its lane, in order");
-            E.line("    const uint32_t i = oni_;");
-            E.line("    if (i == NO_PKT) break;");
-            E.line("    oni_ = NO_PKT;");
-            E.line("    if (j + 1u < oQ_) { const uint64_t x_ = (uint64_t)i + ostr_; if (x_ < olim_) oni_ = (uint32_t)x_; }");
-        } else if (spread_on) {
-            E.line("  for (uint32_t j = 0; j < SPREAD_PPB / 256u; j++) {");
-            E.line("    const uint32_t i = blo_ + j * 256u + threadIdx.x;");
-            E.line("    if (i >= bhi_) break;");
-        } else {
-            E.line("  for (uint32_t j = 0; j < kp.per_lane; j++) {");
-            E.line("    uint32_t i;");
-            E.line("    if (kp.sched == SCHED_CHUNKED) { const uint64_t ii = (uint64_t)g * kp.per_lane + j; if (ii >= kp.n) break; i = (uint32_t)ii; }");
-            E.line("    else if (kp.sched == SCHED_INTERLEAVED) { const uint64_t ii = (uint64_t)j * kp.lanes + (g >= kp.sched_shift ? g - kp.sched_shift : g + kp.lanes - kp.sched_shift); if (ii >= kp.n) break; i = (uint32_t)ii; }");
-            E.line("    else { if (j >= ex_count) break; i = ld_nt(kp.sched_pkts + ex_begin + j); }");
-        }
-        if (lpf_on) {
-            E.line("    uint64_t poff_; uint32_t plen_;");
-            for (uint32_t q = 0; q < xpf.words; q++) E.line("    uint64_t xc%u_ = 0;", q);
-            E.line("    if (j < lpf_n_) {   // parked in LDS when the lane started");
-            E.line("      poff_ = lpfo_[j * 256u + threadIdx.x];");
-            E.line("      const uint32_t lw_ = lpfl_[j * 256u + threadIdx.x];");
-            E.line("      plen_ = lw_ & 0x7fffffffu;");
-            E.line("      xc_ok_ = lw_ >> 31;");
-            for (uint32_t q = 0; q < xpf.words; q++)
-                E.line("      if (xc_ok_) xc%u_ = lpfw_[(j * %uu + %uu) * 256u + threadIdx.x];", q, xpf.words, q);
-            E.line("    } else {");
-            E.line("      poff_ = pkt_off_at(kp, i); plen_ = pkt_len_at(kp, i); xc_ok_ = 0u;");
-            E.line("    }");
-        } else if (pf && xpf.on) {
-            E.line("    const uint64_t poff_ = noff_; const uint32_t plen_ = nlen_;");
-            E.line("    xc_ok_ = xn_ok_;");
-            for (uint32_t q = 0; q < xpf.words; q++) E.line("    const uint64_t xc%u_ = xn%u_;", q, q);
-            E.line("    noff_ = noff2_; nlen_ = nlen2_; nidx_ = nidx2_;");
-            emit_xpf_issue("    ");
-            E.line("    nidx2_ = nidx_ != NO_PKT ? pkt_next(kp, nidx_, j + 2u, ex_begin, ex_count) : NO_PKT;");
-            E.line("    if (nidx2_ != NO_PKT) { noff2_ = pkt_off_at(kp, nidx2_); nlen2_ = pkt_len_at(kp, nidx2_); }");
-        } else if (pf) {
-            if (!spread_own) E.line("    const uint64_t poff_ = pkt_off_take(kp, noff_, i); const uint32_t plen_ = pkt_len_take(kp, nlen_);");
-            if (spread_own) {
-                // (a uniform batch prefetches nothing: its next descriptor is computed at L_term; at a
-                // batch boundary the next batch's form decides, read with its arrays from LDS)
-                E.line("    uint32_t cf_ = ofl_; asm volatile(\"\" : \"+s\"(cf_));");
-                // One load site and one mask for both cases, as before: the two addresses are chosen
-                // first, and both loads are made when the batch has either array.  An array the batch
-                // does not have (one of the two only) is read from the kernarg segment instead, 8 valid
-                // bytes whose value pkt_*_take never looks at.
-                E.line("    const uint64_t *po_ = nullptr; const uint32_t *pl_ = nullptr;");
-                E.line("    if (j + 1u < oQ_) { if (oni_ != NO_PKT && (cf_ & 12u) != 12u) { po_ = (cf_ & 4u) ? (const uint64_t *)&kp : br_.pkt_off + oni_; pl_ = (cf_ & 8u) ? (const uint32_t *)&kp : br_.pkt_len + oni_; } }");
-                E.line("    else if (bt_ + 1u < nb_ && oi_ != NO_PKT) { const BatchRef &nx_ = obr_[bt_ + 1u];");
-                E.line("      if (nx_.pkt_off || nx_.pkt_len) { po_ = nx_.pkt_off ? nx_.pkt_off + oi_ : (const uint64_t *)&kp; pl_ = nx_.pkt_len ? nx_.pkt_len + oi_ : (const uint32_t *)&kp; }");
-                E.line("      bpre_ = true; }");
-                E.line("    if (po_) { pkt_off_pf(true, po_, 0u, noff_); pkt_len_pf(true, pl_, 0u, nlen_); }");
-            }
-            else if (spread_on) E.line("    { const uint32_t n_ = i + 256u; if (n_ < bhi_) pkt_desc_pf(kp, n_, noff_, nlen_); }");
-            else E.line("    { const uint32_t n_ = pkt_next(kp, i, j + 1, ex_begin, ex_count); if (n_ != NO_PKT) pkt_desc_pf(kp, n_, noff_, nlen_); }");
-        }
-        E.line("    const KParams &kq_ = kp;");   // the once-per-packet fields' name in the generated text
-        if (spread_own) {   // the packet's vCPU and its row of the spread map (chunked: per packet)
-            E.line("    { const uint32_t ol_ = ochk_ ? i / oP_ : olane_;");
-            E.line("      srow_ = ol_ - blockIdx.x * oR_;");
-            E.line("      L.cpu = (int32_t)(ocpu_ - olane_ + ol_);");
-            E.line("      sbase_ = SM_.backing_addr + (uint32_t)L.cpu * SM_.addr_period; }");
-        } else if (spread_on) {   // this packet's vCPU (the schedule's lane for it) and its row of the spread map
-            E.line("    { if (kp.sched == SCHED_CHUNKED) lam_ = i / kp.per_lane;");
-            E.line("      else if (j) { lam_ += lstep_; if (lam_ >= kp.cpu_lanes) lam_ -= kp.cpu_lanes; }");
-            E.line("      L.cpu = (int32_t)(kp.vcpu_begin + lam_);");
-            E.line("      srow_ = lam_ >= lam0_ ? lam_ - lam0_ : lam_ + kp.cpu_lanes - lam0_;");
-            E.line("      sbase_ = SM_.backing_addr + (uint32_t)L.cpu * SM_.addr_period; }");
-        }
-        if (ctx == CTX_SKB) {
-            // NewProcess + LinuxContextSKBuff.Load (context_sk_buff.go:42-107, skb.h)
-            E.line("    uint64_t r1 = 0;");
-            if (skb_lds)   // the process's SkbRec into this lane's LDS slot: every field access reads LDS
-                E.line("    const int ls_ = skb_load_lds(kp, L, i, r1, srec_ + %uu * threadIdx.x);", kSrecQ);
-            else
-                E.line("    const int ls_ = skb_load(kp, L, i, r1);");
-        } else {
-            // NewProcess + LinuxContextXDP.Load (vm.go:198-235, context_xdp_md.go:47-115)
-            if (spread_own) {   // a plain launch (ofl_ = 0): no room, no array; only the interface scalars
-                E.line("    uint32_t H = 0u, T = 0u;");
-                E.line("    L.ingress = oin_; L.rxq = orx_; L.egress = oeg_;");
-                E.line("    if (ofl_ & 3u) {");
-                E.line("      H = kq_.headroom_arr ? ld_nt(kq_.headroom_arr + i) : kq_.headroom;");
-                E.line("      T = kq_.tailroom_arr ? ld_nt(kq_.tailroom_arr + i) : kq_.tailroom;");
-                E.line("      if (kq_.ingress_arr) L.ingress = (uint32_t)ld_nt(kq_.ingress_arr + i);");
-                E.line("      if (kq_.rxq_arr) L.rxq = (uint32_t)ld_nt(kq_.rxq_arr + i);");
-                E.line("      if (kq_.egress_arr) L.egress = (uint32_t)ld_nt(kq_.egress_arr + i);");
-                E.line("    }");
-            } else {
-            E.line("    const uint32_t H = kq_.headroom_arr ? ld_nt(kq_.headroom_arr + i) : kq_.headroom;");
-            E.line("    const uint32_t T = kq_.tailroom_arr ? ld_nt(kq_.tailroom_arr + i) : kq_.tailroom;");
-            }
-            if (pf) {
-                E.line("    const uint32_t len = plen_;");
-                E.line("    L.pkt = %s + poff_;", spread_own ? "br_.pkt_data" : "kq_.pkt_data");
-            } else if (spread_own) {
-                E.line("    const uint32_t len = pkt_len_at(!(ofl_ & 8u), br_.pkt_len, clen_, i);");
-                E.line("    L.pkt = br_.pkt_data + pkt_off_at(!(ofl_ & 4u), br_.pkt_off, cstr_, i);");
-            } else {
-                E.line("    const uint32_t len = pkt_len_at(kq_, i);");
-                E.line("    L.pkt = kq_.pkt_data + pkt_off_at(kq_, i);");
-            }
-            E.line("    L.M = H + len + T;");
-            E.line("    L.pa = P;");
-            E.line("    L.rec = nullptr;");
-            if (spread_own) E.line("    if (ofl_ & 3u) {");   // (no rooms to zero in a plain launch)
-            E.line("    for (uint32_t b = 0; b < H; b++) *gp(L.pkt + b) = 0;");
-            E.line("    for (uint32_t b = 0; b < T; b++) *gp(L.pkt + H + len + b) = 0;");
-            if (spread_own) E.line("    }");
-            E.line("    L.data = P + H;");
-            E.line("    L.data_end = P + H + len;");
-            if (!spread_own) {
-            E.line("    L.ingress = (uint32_t)(kq_.ingress_arr ? ld_nt(kq_.ingress_arr + i) : kq_.ingress);");
-            E.line("    L.rxq = (uint32_t)(kq_.rxq_arr ? ld_nt(kq_.rxq_arr + i) : kq_.rxq);");
-            E.line("    L.egress = (uint32_t)(kq_.egress_arr ? ld_nt(kq_.egress_arr + i) : kq_.egress);");
-            }
-            E.line("    uint64_t r1 = P + L.M + 1;");
-        }
+    }
+    // the descriptor pipeline over kp's arrays: the first packet's prefetch ahead of the loop, then per
+    // packet the take and the next one's prefetch (next: its index, ok: that there is one)
+    void emit_pf_first(const char *next, const char *ok) {
+        E.line("  uint64_t noff_ = 0; uint32_t nlen_ = 0;");
+        E.line("  { const uint32_t n_ = %s; if (%s) pkt_desc_pf(kp, n_, noff_, nlen_); }", next, ok);
+    }
+    void emit_pf_next(const char *next, const char *ok) {
+        E.line("    const uint64_t poff_ = pkt_off_take(kp, noff_, i); const uint32_t plen_ = pkt_len_take(kp, nlen_);");
+        E.line("    { const uint32_t n_ = %s; if (%s) pkt_desc_pf(kp, n_, noff_, nlen_); }", next, ok);
+    }
+    void emit_kq() { E.line("    const KParams &kq_ = kp;"); }   // the once-per-packet fields' name in the generated text
+    // NewProcess + LinuxContextSKBuff.Load (context_sk_buff.go:42-107, skb.h)
+    void emit_skb_load() {
+        E.line("    uint64_t r1 = 0;");
+        if (skb_lds)   // the process's SkbRec into this lane's LDS slot: every field access reads LDS
+            E.line("    const int ls_ = skb_load_lds(kp, L, i, r1, srec_ + %uu * threadIdx.x);", kSrecQ);
+        else
+            E.line("    const int ls_ = skb_load(kp, L, i, r1);");
+    }
+    // NewProcess + LinuxContextXDP.Load (vm.go:198-235, context_xdp_md.go:47-115) from kp's scalars and arrays
+    void emit_xdp_load() {
+        E.line("    const uint32_t H = kq_.headroom_arr ? ld_nt(kq_.headroom_arr + i) : kq_.headroom;");
+        E.line("    const uint32_t T = kq_.tailroom_arr ? ld_nt(kq_.tailroom_arr + i) : kq_.tailroom;");
+        emit_xdp_extent("kq_.pkt_data", "pkt_len_at(kq_, i)", "pkt_off_at(kq_, i)", nullptr);
+        E.line("    L.ingress = (uint32_t)(kq_.ingress_arr ? ld_nt(kq_.ingress_arr + i) : kq_.ingress);");
+        E.line("    L.rxq = (uint32_t)(kq_.rxq_arr ? ld_nt(kq_.rxq_arr + i) : kq_.rxq);");
+        E.line("    L.egress = (uint32_t)(kq_.egress_arr ? ld_nt(kq_.egress_arr + i) : kq_.egress);");
+    }
+    // ... its part from the packet's length and address to data_end, given H and T (data, len_at,
+    // off_at: the batch's arrays; rooms_if: the test under which there can be rooms to zero)
+    void emit_xdp_extent(const char *data, const char *len_at, const char *off_at, const char *rooms_if) {
+        E.line("    const uint32_t len = %s;", pf ? "plen_" : len_at);
+        if (pf) E.line("    L.pkt = %s + poff_;", data);
+        else E.line("    L.pkt = %s + %s;", data, off_at);
+        E.line("    L.M = H + len + T;");
+        E.line("    L.pa = P;");
+        E.line("    L.rec = nullptr;");
+        if (rooms_if) E.line("    %s {", rooms_if);
+        E.line("    for (uint32_t b = 0; b < H; b++) *gp(L.pkt + b) = 0;");
+        E.line("    for (uint32_t b = 0; b < T; b++) *gp(L.pkt + H + len + b) = 0;");
+        if (rooms_if) E.line("    }");
+        E.line("    L.data = P + H;");
+        E.line("    L.data_end = P + H + len;");
+    }
+    // the process's registers and state (r1: the context pointer, unless the load declared it;
+    // r10_decl: the line(s) that declare r10)
+    void emit_process_start(const char *r1, const char *r10_decl) {
+        if (r1) E.line("    uint64_t r1 = %s;", r1);
         E.line("    SM0(L) = 0; SM1(L) = 0; L.xdp_dirty = 0; L.nframes = 0; L.tailcalls = 0; L.t_lo = 0; L.t_n = 0; L.t_ptr = nullptr;");
         E.line("    uint64_t r0 = 0, r2 = 0, r3 = 0, r4 = 0, r5 = 0, r6 = 0, r7 = 0, r8 = 0, r9 = 0;");
-        // (the owned form's copy is pinned again per packet: the stack arithmetic of the cold paths
-        // would otherwise be hoisted out of the loop, one live SGPR per derived value)
-        if (spread_own) E.line("    uint32_t lr10_ = or10_; asm volatile(\"\" : \"+s\"(lr10_));");
-        E.line("    uint64_t r10 = %s;", spread_own ? "lr10_" : "kp.static_next + kp.frame_size");
+        E.line("%s", r10_decl);
         E.line("    uint32_t steps = 0;");
         if (census) E.line("    coldn_ = 0;");
         if (!spec_use.empty()) E.line("    spv_ = 1;");
@@ -719,32 +852,32 @@ class Gen {
         // there (vm.go:344-349); a launch without contexts skips this on a uniform scalar test
         // (a variant of its own, built for launches given contexts: the check costs ~2 % on cfg 2)
         if (ctx_check) E.line("    { const uint32_t cz_ = ctx_done(kq_, i); if (cz_) TERM(MIMIC_ERR_CANCELED - 1u + cz_, 0); }");
-        if (dispatch_on()) {
-            // one dispatch block for the entry and every tail call (see dispatch_on)
-            E.line("    uint32_t cur_;   // no initializer: the TERM gotos above jump past it");
-            E.line("    cur_ = %s;", spread_own ? "oep_" : "kp.entry_prog");
-            E.line("    switch (cur_) {");
-            for (auto &p : P)
-                if (p.n == 0) E.line("    case %u: steps = 1; TERM(MIMIC_ERR_PC_OOB, 0);", p.id);  // vm.go:297-299
-            E.line("%s", nonempty_cases().c_str());
-            E.line("      break;");
-            E.line("    default: TERM(MIMIC_ERR_PC_OOB, 0);");
-            E.line("    }");
-            E.line("  D_:");
-            E.line("    switch (cur_) {");
-            for (auto &p : P)
-                if (p.n) E.line("    case %u: goto P%u_0;", p.id, p.id);
-            E.line("    default: TERM(MIMIC_ERR_ENGINE_HELPER, -1);");
-            E.line("    }");
-        } else {
-            E.line("    switch (%s) {", spread_own ? "oep_" : "kp.entry_prog");
-            for (auto &p : P) {
-                if (p.n == 0) E.line("    case %u: steps = 1; TERM(MIMIC_ERR_PC_OOB, 0);", p.id);  // vm.go:297-299
-                else E.line("    case %u: goto P%u_0;", p.id, p.id);
-            }
-            E.line("    default: TERM(MIMIC_ERR_PC_OOB, 0);");
-            E.line("    }");
+    }
+    void emit_entry_dispatch(const char *entry) {
+        // with tail calls: one dispatch block (D_) for the entry and every tail call (see dispatch_knob),
+        // which the entry's own switch only falls into
+        const bool d = dispatch_on();
+        if (d) E.line("    uint32_t cur_;   // no initializer: the TERM gotos above jump past it");
+        if (d) E.line("    cur_ = %s;", entry);
+        E.line("    switch (%s) {", d ? "cur_" : entry);
+        for (auto &p : P) {
+            if (p.n == 0) E.line("    case %u: steps = 1; TERM(MIMIC_ERR_PC_OOB, 0);", p.id);  // vm.go:297-299
+            else if (!d) E.line("    case %u: goto P%u_0;", p.id, p.id);
         }
+        if (d) E.line("%s", nonempty_cases().c_str());
+        if (d) E.line("      break;");
+        E.line("    default: TERM(MIMIC_ERR_PC_OOB, 0);");
+        E.line("    }");
+        if (!d) return;
+        E.line("  D_:");
+        E.line("    switch (cur_) {");
+        for (auto &p : P)
+            if (p.n) E.line("    case %u: goto P%u_0;", p.id, p.id);
+        E.line("    default: TERM(MIMIC_ERR_ENGINE_HELPER, -1);");
+        E.line("    }");
+    }
+    // every program's slots, then the packet's two ways out of them
+    void emit_programs() {
         for (auto &p : P) program(p);
         E.line("    TERM(MIMIC_ERR_ENGINE_HELPER, -1);");
         if (defer_mode) {
@@ -754,112 +887,40 @@ class Gen {
             E.line("    break;");
         }
         E.line("  L_term:");
-        // the owned form takes the next packet's descriptor here, ahead of the result stores: the
-        // wait for it (it came back with this packet's first loads) is the last one before the next
-        // packet's window loads, which the stores' acknowledgements then travel with
-        // (a uniform batch: index * stride and the one length instead; after a batch's last packet the
-        // next batch's top sets both)
-        // (the form bits pinned again here: a copy held from the loop top would be one more live SGPR)
-        if (spread_own && pf) E.line("    { uint32_t ct_ = ofl_; asm volatile(\"\" : \"+s\"(ct_)); poff_ = pkt_off_take(!(ct_ & 4u), noff_, cstr_, oni_); plen_ = pkt_len_take(!(ct_ & 8u), nlen_, clen_); asm volatile(\"\" : \"+v\"(poff_), \"+v\"(plen_)); }");
+    }
+    // rb: what holds the result arrays' addresses (rb_decl: its declaration, when the block needs one)
+    void emit_result_stores(const char *rb, const char *rb_decl) {
         E.line("    {");
-        {   // the owned form's results go to the batch of this iteration, its addresses read from the
-            // block's LDS copy of the batch references (obr_): no SGPR holds them across the loop
-            const char *rb = spread_own ? "lb_" : "kq_";
-            // (by reference: each address is read just ahead of its store)
-            if (spread_own) E.line("    const BatchRef &lb_ = obr_[bt_];");
-            if (ntres) {
-                E.line("    if (%s.r0) st_nt(%s.r0 + i, r0);", rb, rb);
-                E.line("    if (%s.status) st_nt(%s.status + i, (uint8_t)st_);", rb, rb);
-            } else {
-                E.line("    if (%s.r0) *gp(%s.r0 + i) = r0;", rb, rb);
-                E.line("    if (%s.status) *gp(%s.status + i) = (uint8_t)st_;", rb, rb);
-            }
-            if (census) E.line("    if (%s.steps) st_nt(%s.steps + i, coldn_);   // census: slow-path calls, not steps", rb, rb);
-            else E.line("    if (%s.steps) st_nt(%s.steps + i, steps);", rb, rb);
-            E.line("    if (%s.err_pc) st_nt(%s.err_pc + i, epc_);", rb, rb);
+        if (rb_decl) E.line("%s", rb_decl);
+        if (ntres) {
+            E.line("    if (%s.r0) st_nt(%s.r0 + i, r0);", rb, rb);
+            E.line("    if (%s.status) st_nt(%s.status + i, (uint8_t)st_);", rb, rb);
+        } else {
+            E.line("    if (%s.r0) *gp(%s.r0 + i) = r0;", rb, rb);
+            E.line("    if (%s.status) *gp(%s.status + i) = (uint8_t)st_;", rb, rb);
         }
+        if (census) E.line("    if (%s.steps) st_nt(%s.steps + i, coldn_);   // census: slow-path calls, not steps", rb, rb);
+        else E.line("    if (%s.steps) st_nt(%s.steps + i, steps);", rb, rb);
+        E.line("    if (%s.err_pc) st_nt(%s.err_pc + i, epc_);", rb, rb);
         E.line("    }");
-        if (proc) {   // Process.Run: the whole state (interp.hip step_save), the process done
-            E.line("    if (kq_.step) { StepState *S_ = kq_.step;");
-            E.line("      S_->r[0] = r0; S_->r[1] = r1; S_->r[2] = r2; S_->r[3] = r3; S_->r[4] = r4; S_->r[5] = r5;");
-            E.line("      S_->r[6] = r6; S_->r[7] = r7; S_->r[8] = r8; S_->r[9] = r9; S_->r[10] = r10;");
-            E.line("      S_->pc = epc_; S_->prog = pg_; S_->steps = steps; S_->status = st_; S_->started = 1u; S_->finished = 1u; }");
-        }
+    }
+    // Process.Run: the whole state (interp.hip step_save), the process done
+    void emit_proc_store() {
+        E.line("    if (kq_.step) { StepState *S_ = kq_.step;");
+        E.line("      S_->r[0] = r0; S_->r[1] = r1; S_->r[2] = r2; S_->r[3] = r3; S_->r[4] = r4; S_->r[5] = r5;");
+        E.line("      S_->r[6] = r6; S_->r[7] = r7; S_->r[8] = r8; S_->r[9] = r9; S_->r[10] = r10;");
+        E.line("      S_->pc = epc_; S_->prog = pg_; S_->steps = steps; S_->status = st_; S_->started = 1u; S_->finished = 1u; }");
+    }
+    void emit_loop_close() {
         E.line("    lane_steps += steps;");
         E.line("  }");
-        if (spread_own) E.line("  }   // batches");
-        if (vc_on) E.line("  VC_FLUSH();");
-        if (spread_own) {
-            // the block's rows into the map: plain read-modify-writes (the block owns these vCPUs)
-            E.line("  __syncthreads();");
-            E.line("  if (ofw_ && sacc_[threadIdx.x]) *ofd_ = ofv_ + sacc_[threadIdx.x];");
-            E.line("  for (uint32_t w_ = threadIdx.x + 256u; w_ < oR_ * SPREAD_ROWW; w_ += 256u) {   // rows past 256 words");
-            E.line("    const spread_t v_ = sacc_[w_];");
-            E.line("    if (!v_) continue;");
-            E.line("    const uint32_t r_ = w_ / SPREAD_ROWW, q_ = w_ - r_ * SPREAD_ROWW;");
-            E.line("    GAS spread_t *d_ = (GAS spread_t *)(kp.arena + SM_.dev_off + (size_t)(kp.vcpu_begin + blockIdx.x * oR_ + r_) * SM_.dev_stride) + q_;");
-            E.line("    *d_ += v_;");
-            E.line("  }");
-        } else if (spread_on) {
-            // the block's counters into the map: one agent-scope add per non-zero counter (a row's
-            // counters are contiguous in the arena, so consecutive threads add consecutive words)
-            E.line("#if SPREAD_ROWS");
-            E.line("  __syncthreads();");
-            // a table that covers every vCPU lane (V <= packets per block): the block writes it,
-            // rotated to absolute lanes, into its slice of kp.spread_part with plain stores, and
-            // mimic_spread_reduce_kernel adds the blocks' slices into the map (one agent-scope add per
-            // counter per group of blocks, not per block: the per-block adds were 43 % of the kernel)
-            E.line("  if (kp.spread_part && kp.cpu_lanes == SPREAD_ROWS) {");
-            E.line("    spread_t *pt_ = (spread_t *)kp.spread_part + (size_t)blockIdx.x * (SPREAD_ROWS * SPREAD_ROWW);");
-            E.line("    for (uint32_t w_ = threadIdx.x; w_ < SPREAD_ROWS * SPREAD_ROWW; w_ += 256u) {");
-            E.line("      const uint32_t r_ = w_ / SPREAD_ROWW, q_ = w_ - r_ * SPREAD_ROWW;");
-            E.line("      const uint32_t lr_ = lam0_ + r_ < SPREAD_ROWS ? lam0_ + r_ : lam0_ + r_ - SPREAD_ROWS;");
-            E.line("      pt_[lr_ * SPREAD_ROWW + q_] = sacc_[w_];");
-            E.line("    }");
-            E.line("  } else");
-            E.line("  for (uint32_t w_ = threadIdx.x; w_ < SPREAD_ROWS * SPREAD_ROWW; w_ += 256u) {");
-            E.line("    const spread_t v_ = sacc_[w_];");
-            E.line("    if (!v_) continue;");
-            E.line("    const uint32_t r_ = w_ / SPREAD_ROWW, q_ = w_ - r_ * SPREAD_ROWW;");
-            E.line("    const uint32_t lr_ = lam0_ + r_ < kp.cpu_lanes ? lam0_ + r_ : lam0_ + r_ - kp.cpu_lanes;");
-            E.line("    spread_t *d_ = (spread_t *)(kp.arena + SM_.dev_off + (size_t)(kp.vcpu_begin + lr_) * SM_.dev_stride) + q_;");
-            E.line("    __hip_atomic_fetch_add((GAS spread_t *)d_, v_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);");
-            E.line("  }");
-            E.line("#endif");
-        }
+    }
+    void emit_kernel_close() {
         E.line("  if (kp.lane_steps) st_nt(kp.lane_steps + g, lane_steps);");
         if (hash_chunk) E.line("  h_chunk_fini();   // the block's last wave hands its chunk's remainder back");
         E.line("}");
-        if (spread_own) {
-            // own_hoist: the instruction-table words the emitted programs use (an LD_IMM64 slot's
-            // constant, own_k; its map hint, own_h -- only the half that is used), read once ahead of
-            // the batch loop and pinned in SGPRs
-            std::string hs;
-            char b[512];
-            for (uint32_t s : own_k) {
-                snprintf(b, sizeof b, "  uint64_t hk%u_ = cget(kp.insns, %uu).k; asm volatile(\"\" : \"+s\"(hk%u_));\n", s, s, s);
-                hs += b;
-            }
-            for (uint32_t s : own_h) {
-                snprintf(b, sizeof b, "  uint32_t hh%u_ = AUX_MAPHINT(cget(kp.insns, %uu).aux); asm volatile(\"\" : \"+s\"(hh%u_));\n", s, s, s);
-                hs += b;
-            }
-            if (!hs.empty()) hs.pop_back();
-            const size_t q = E.s.find(kOwnHoist);
-            E.s.replace(q, strlen(kOwnHoist), hs);
-        }
-        if (census) {   // diagnostics: each slow-path call adds 1 to its kind's 4-bit field of coldn_
-            static const char *kinds[] = {"cold_load(", "cold_store(", "cold_lookup(", "cold_update(", "cold_delete(",
-                                          "cold_tailcall(", "cold_ldabs(", "cold_adjust_tail("};
-            for (int k = 0; k < 8; k++) {
-                const std::string from = std::string("COLD_CALL(") + kinds[k], to = "COLD_CALL_K(" + std::to_string(4 * k) + ", " + kinds[k];
-                for (size_t q = E.s.find(from); q != std::string::npos; q = E.s.find(from, q + to.size())) E.s.replace(q, from.size(), to);
-            }
-        }
-        return E.s;
     }
 
-  private:
     const std::vector<ProgView> &P;
     Emitter E;
     // packet-entry fast paths: the entry's address, the window's offset in packet memory, and
@@ -871,8 +932,7 @@ class Gen {
     static constexpr uint32_t SKB_HEADROOM_J = 32;
     bool any_tail = false, any_local = false, all_leaders = false;
     // owned form: slots whose instruction-table constant (own_k) or map hint (own_h) the kernel
-    // reads once per launch; their declarations replace kOwnHoist when the programs are out
-    static constexpr const char *kOwnHoist = "  //@own_hoist@";
+    // reads once per launch (emit_owned declares them ahead of the batch loop)
     std::set<uint32_t> own_k, own_h;
     uint32_t blk_start = 0;   // first slot of the basic block being emitted
     uint32_t cur_prog = 0;    // program being emitted
@@ -1601,6 +1661,13 @@ class Gen {
     // the slow path of slot i of the program being emitted: a call (COLD_CALL) or a deferral
     std::string cold(const std::string &call, uint32_t i) const {
         if (defer_mode) return defer_text(i);
+        if (census) {   // COLD_CALL_K counts the call under its kind, 4 bits each (emit_lane_open)
+            static const char *kinds[] = {"cold_load(", "cold_store(", "cold_lookup(", "cold_update(", "cold_delete(",
+                                          "cold_tailcall(", "cold_ldabs(", "cold_adjust_tail("};
+            for (int k = 0; k < 8; k++)
+                if (!call.compare(0, strlen(kinds[k]), kinds[k]))
+                    return "COLD_CALL_K(" + std::to_string(4 * k) + ", " + call + ", " + std::to_string(i) + ");";
+        }
         return "COLD_CALL(" + call + ", " + std::to_string(i) + ");";
     }
     std::string defer_text(uint32_t i) const {

@@ -231,3 +231,51 @@ def test_context_variant_compiles():
     assert "ctx_done(" not in _source([loop])
     _compiles(s_loop)
     _compiles(s_straight)
+
+
+def test_source_fingerprint_matrix_is_not_vacuous(monkeypatch):
+    """tools/jit_fingerprint.py --source compares kernel sources under a knob matrix; the comparison
+    means something only if the corpus holds every form of kernel and every setting reaches the
+    generator.  Checked here on the eight bench kernels plus the suite's smallest program set with a
+    BPF-to-BPF call (MIMIC_JIT_RETDISPATCH changes none of the bench kernels).  MIMIC_JIT_CTXCHECK is
+    read once per process: test_context_variant_compiles covers it."""
+    import importlib
+    import os
+    import sys
+
+    from mimic_amd import jit as J
+
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+    import jit_fingerprint as FP
+
+    def local_call(raws):
+        return any(r[o] == 0x85 and r[o + 1] >> 4 == 1 for r in raws for o in range(0, len(r), 8))
+
+    calls = min((k for k in importlib.import_module("test_gpu_parity").jit_kernels() if local_call(k[0])),
+                key=lambda k: sum(len(r) for r in k[0]))
+
+    def under(setting):
+        for name in [n for n in os.environ if n.startswith("MIMIC_JIT_")]:
+            monkeypatch.delenv(name)
+        for name, value in FP.knob_env(setting).items():
+            monkeypatch.setenv(name, value)
+        return dict(FP.bench_sources(), local_call=J.kernel_source(list(calls[0]), *calls[1:]))
+
+    assert FP.KNOBS[0] == "" and len(FP.KNOBS) == 29 and len(set(FP.KNOBS)) == 29
+    base = under("")
+    bench = [s for label, s in base.items() if label.startswith("bench:")]
+    assert len(bench) == 8
+    spread = [s for s in bench if "#define MIMIC_SPREAD 1" in s]
+    assert any("#define MIMIC_SPREAD_OWN 1" in s for s in spread)          # owned
+    assert any("#define MIMIC_SPREAD_OWN 1" not in s for s in spread)      # table spread
+    assert len(spread) < len(bench)                                        # one-lane
+    assert any("S_->pc" in s for s in bench)                               # single-process
+    assert any("#define MIMIC_CTX_FIXED 1" in s for s in bench)            # sk_buff
+    for setting in FP.KNOBS[1:]:
+        alt = under(setting)
+        if setting != "CTXCHECK=1":
+            assert any(alt[label] != base[label] for label in base), setting
+        if setting == "LPF=1":
+            assert any("lpfo_" in s for s in alt.values()) and not any("lpfo_" in s for s in base.values())
+        if setting == "XPF=1":
+            assert any("xpf_on_" in s for s in alt.values()) and not any("xpf_on_" in s for s in base.values())

@@ -1,19 +1,31 @@
-"""Fingerprints of the JIT kernels' machine code, on a CPU host (hipRTC needs no GPU).
+"""Fingerprints of the JIT kernels, on a CPU host (neither mode needs a GPU).
 
-    python tools/jit_fingerprint.py OUT.json
+    python tools/jit_fingerprint.py OUT.json            machine code
+    python tools/jit_fingerprint.py --source OUT.json   source text, under every knob setting
 
-For every kernel the GPU suite compiles (the jit_kernels() of each tests/test_gpu_*.py module, what
-the session prewarm collects) and every bench kernel, OUT.json records the sha256 and size of the
-gfx950 code object's .text section and its jit.kernel_resources.  Two libraries (MIMIC_LIB selects
+Machine code.  For every kernel the GPU suite compiles (the jit_kernels() of each
+tests/test_gpu_*.py module, what the session prewarm collects) and every bench kernel, OUT.json
+records the sha256 and size of the gfx950 code object's .text section and its jit.kernel_resources.  Two libraries (MIMIC_LIB selects
 one) whose files are equal generate the same machine code for all of them: a refactor of the
 generator or of the device runtime headers can be shown to change no kernel without a GPU.  Whole
-code objects are not compared: their other sections change with a comment in the source."""
+code objects are not compared: their other sections change with a comment in the source.  This is
+the mode for a change that may alter the generated text (a comment, an alias, indentation) or a
+runtime header, and must leave the code as it was.
+
+Source.  No compile: for every label of sources(), under each setting of KNOBS (one child process
+per setting, its environment cleared of every other MIMIC_JIT_ variable), OUT.json records the
+sha256 and byte length of the source text; the file's own sha256 is printed.  The source text
+is the code-object cache key, so two libraries whose files are equal generate the same kernels,
+cache entries and speed under every knob: this is the mode for a refactor of the generator (jit.cpp)
+that touches no runtime header, and it proves nothing about a change to one (the headers are
+included by the text, not part of it)."""
 import glob
 import hashlib
 import importlib
 import json
 import os
 import struct
+import subprocess
 import sys
 import tempfile
 
@@ -21,6 +33,18 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
 from mimic_amd import _lib, jit as J, workloads as W  # noqa: E402
+
+
+# the knob matrix of the source mode: "" is the default, every other name carries the MIMIC_JIT_ prefix
+KNOBS = ("", "FAST=0", "PREFETCH=0", "XPF=1", "LPF=1", "NTRES=0", "CENSUS=1", "CTXCHECK=1", "COLD=call", "COLD=inline",
+         "COLD=defer", "DISPATCH=0", "RETDISPATCH=1", "VC=0", "LDSSTK=0", "SKBLDS=0", "SMLDS=0", "SPEC=0", "COMBINE=0",
+         "HCHUNK=0", "WAVES=2", "DEFS=A,B=2", "INC=0", "FWD=0", "ELIDE=0", "WINDOW=0", "HASH=0", "TAIL=0", "SKBFIELD=0")
+
+
+def knob_env(setting: str) -> dict:
+    """The environment variable a KNOBS entry sets ({} for the default)."""
+    name, _, value = setting.partition("=")
+    return {"MIMIC_JIT_" + name: value} if setting else {}
 
 
 def text_section(elf: bytes) -> bytes:
@@ -42,6 +66,13 @@ def sources():
         fn = getattr(importlib.import_module(name), "jit_kernels", None)
         for n, k in enumerate(fn() if fn else []):
             out[f"{name}[{n}]"] = J.kernel_source(list(k[0]), *k[1:])
+    out.update(bench_sources())
+    return out
+
+
+def bench_sources():
+    """{label: kernel source} of the bench configs' kernels."""
+    out = {}
     cls, p5, ft = W.prog_classifier(), W.prog_parse5(), W.prog_flowtrack()
     skb = [p.raw for p in W.skb_programs()[0]]
     progs = [(cls.raw, cls.relocs)]
@@ -64,7 +95,31 @@ def fingerprint(src: str) -> dict:
     return {"text_sha256": hashlib.sha256(text).hexdigest(), "text_bytes": len(text), "resources": J.kernel_resources(code)}
 
 
+def source_digests() -> dict:
+    """{label: sha256 and length of its source} under this process's environment."""
+    return {label: {"sha256": hashlib.sha256(s.encode()).hexdigest(), "bytes": len(s.encode())} for label, s in sources().items()}
+
+
+def source_mode(out_path: str) -> None:
+    clean = {k: v for k, v in os.environ.items() if not k.startswith("MIMIC_JIT_")}
+    doc = {}
+    for setting in KNOBS:   # a child each: MIMIC_JIT_CTXCHECK is read once per process
+        out = subprocess.run([sys.executable, os.path.abspath(__file__), "--source-child"], env=dict(clean, **knob_env(setting)),
+                             capture_output=True, text=True, check=True).stdout
+        doc[setting or "default"] = json.loads(out.strip().splitlines()[-1])
+    body = json.dumps(doc, indent=1, sort_keys=True) + "\n"
+    with open(out_path, "w") as f:
+        f.write(body)
+    print(f"{len(doc['default'])} kernels x {len(doc)} settings -> {out_path}, sha256 {hashlib.sha256(body.encode()).hexdigest()}")
+
+
 if __name__ == "__main__":
+    if sys.argv[1] == "--source-child":
+        print(json.dumps(source_digests()))
+        sys.exit(0)
+    if sys.argv[1] == "--source":
+        source_mode(sys.argv[2])
+        sys.exit(0)
     srcs = sources()
     distinct = sorted(set(srcs.values()))
     # a cache of this run's own: every kernel is compiled by the library under test, in jit.py's
