@@ -141,6 +141,22 @@ struct HipFence : BlkFence {
 
 }  // namespace
 
+// A JIT kernel the VM keeps for its program set.  Every form is built on first use through
+// kern_build() and dropped with the program set (upload_tables).
+struct JitKernel {
+    int state = 0;   // 0 not built, 1 built, -1 this program set does not allow it
+    hipFunction_t fn = nullptr;
+    JitInfo info{};  // (a spread kernel's LDS table rows: info.spread_rows)
+};
+enum KernForm {
+    K_LANE,              // + CtxKind: one lane per vCPU
+    K_CX = K_LANE + 2,   // + CtxKind: the same with the Run(ctx) check (launches given contexts)
+    K_PROC = K_CX + 2,   // the single-process form (Process.Run)
+    K_SPREAD,            // the table spread kernel (jit.cpp analyze_spread, xdp_md only)
+    K_OWN,               // its owned form (SpreadReq::own)
+    K_FORMS
+};
+
 struct mimic_vm {
     mimic_vm_settings s;
     std::string err;
@@ -177,31 +193,16 @@ struct mimic_vm {
     int exec_mode = MIMIC_EXEC_JIT;
     std::vector<DInsn> h_all;   // predecoded instruction slots of every program (host copy)
     std::vector<DProg> h_dp;
-    hipFunction_t jit_fn[2] = {nullptr, nullptr};   // per CtxKind, generated on first use
-    JitInfo jit_info[2]{};
-    hipFunction_t jit_fn_cx[2] = {nullptr, nullptr};   // the same with the Run(ctx) check (launches given contexts)
-    JitInfo jit_info_cx[2]{};
+    JitKernel kern[K_FORMS];    // the program set's JIT kernels
     // Process.Run tiering (process_advance): a fresh xdp_md process runs on the interpreter's
     // stepping kernel until the VM has made proc_jit_after Runs, then on the program set's
     // single-process JIT form (jit.cpp Gen::proc) -- a compiled program instead of ~0.7 us of
     // interpretation per step.  MIMIC_PROC_JIT=N at VM creation (default 32; 0 at once, -1
-    // never).  proc_jit: 0 not built, 1 built and usable, -1 not usable for this program set
+    // never).
     int64_t proc_jit_after = 32;
     uint64_t proc_runs = 0;
-    int proc_jit = 0;
-    hipFunction_t jit_fn_proc = nullptr;
-    JitInfo jit_info_proc{};
-    // the spread kernel (jit.cpp analyze_spread, xdp_md only): 0 not built yet, 1 built, -1 the
-    // program set does not allow it; spread_bad is the device word a spread launch marks when a
-    // generic access reached per-CPU memory (spread_used: some launch could have marked it)
-    int spread_state = 0;
-    hipFunction_t jit_fn_spread = nullptr;
-    JitInfo jit_info_spread{};
-    // the owned form of the spread kernel (SpreadReq::own): state as spread_state; its LDS table rows
-    int spread_own_state = 0;
-    hipFunction_t jit_fn_spread_own = nullptr;
-    JitInfo jit_info_spread_own{};
-    uint32_t spread_own_rows = 0;
+    // spread_bad is the device word a spread launch marks when a generic access reached per-CPU
+    // memory (spread_used: some launch could have marked it)
     uint32_t *d_spread_bad = nullptr;
     void *d_spread_part = nullptr;   // spread launches: the blocks' counter tables (mimic_spread_reduce_kernel)
     uint64_t spread_part_cap = 0;
@@ -218,7 +219,6 @@ struct mimic_vm {
     std::unordered_map<uint64_t, size_t> pend_at;
     bool host_dirty = false;   // some pending write or dirty hash image
     int spread_mode = -1;   // mimic_set_spread: -1 the default policy (env MIMIC_SPREAD), 0 never, 1 whenever allowed
-    bool spread_lds = false;   // the spread kernel keeps a block's counters in LDS (else agent-scope atomics)
     int last_exec = 0;          // the kernel the last batch ran on
     // launch parameters of the batch interpreter in device memory: a ring of slots written by
     // stream-ordered copies from pinned host memory (a repeated batch reuses its slot)
@@ -585,14 +585,7 @@ static int upload_tables(mimic_vm *vm) {
             }
         }
     }
-    vm->jit_fn[0] = vm->jit_fn[1] = nullptr;
-    vm->jit_fn_cx[0] = vm->jit_fn_cx[1] = nullptr;
-    vm->jit_fn_proc = nullptr;
-    vm->proc_jit = 0;
-    vm->jit_fn_spread = nullptr;
-    vm->spread_state = 0;
-    vm->jit_fn_spread_own = nullptr;
-    vm->spread_own_state = 0;
+    for (JitKernel &k : vm->kern) k = JitKernel{};   // built from the tables above: again on first use
     std::vector<DInsn> all = vm->h_all;
     std::vector<DProg> dp = vm->h_dp;
     all.push_back(DInsn{0, 0, 0});  // keep the array non-empty
@@ -1694,7 +1687,7 @@ struct StepRun {    // a stepped single process (mimic_process_*): its state, pr
     const uint8_t *img = nullptr;
     uint8_t *img_dst = nullptr;
     uint32_t img_n = 0;
-    // Process.Run of a fresh xdp_md process on the single-process JIT form (vm->jit_fn_proc) on
+    // Process.Run of a fresh xdp_md process on the single-process JIT form (vm->kern[K_PROC]) on
     // vCPU `cpu` (this engine's): a one-lane batch whose exit writes the state
     bool jit = false;
     int32_t cpu = 0;
@@ -1903,6 +1896,50 @@ static PrivPlan priv_plan(const mimic_vm *vm) {
     return p;
 }
 
+// The LD_IMM64 slots whose map hint names a per-CPU array, as what is built from them: vc = for
+// the lane value cache, (kernel-wide index, E * S) of those whose row it can hold; seed = a spread
+// kernel's candidates (slot_map, shape), those whose values the arena keeps 8-byte aligned, and
+// row = the longest E * S among them
+struct PercpuSlots {
+    std::vector<std::pair<uint32_t, uint32_t>> vc;
+    SpreadReq seed;
+    uint32_t row = 0;
+};
+static PercpuSlots percpu_slots(const mimic_vm *vm) {
+    PercpuSlots out;
+    for (size_t s = 0; s < vm->h_all.size(); s++) {
+        const DInsn &x = vm->h_all[s];
+        const uint32_t mh = AUX_MAPHINT(x.aux);
+        if (AUX_H(x.aux) != H_LDIMM || !mh || mh > vm->maps.size()) continue;
+        const HostMap &hm = vm->maps[mh - 1];
+        const uint32_t rb = hm.max_entries * hm.value_size;
+        if (vc_row_ok(hm.family, hm.max_entries, hm.value_size)) out.vc.push_back({(uint32_t)s, rb});
+        const DMap dm = to_dmap(hm);
+        if (hm.family != FAM_PERCPU_ARRAY || (dm.dev_off & 7) || (dm.dev_stride & 7)) continue;
+        out.seed.slot_map[(uint32_t)s] = mh - 1;
+        out.seed.shape[mh - 1] = {rb, hm.value_size};
+        out.row = std::max(out.row, rb);
+    }
+    return out;
+}
+
+// The one way a kernel gets into vm->kern: options -> source -> hipRTC build -> record.  A form
+// the programs do not allow (no spread kernel, no usable single-process form) leaves the record
+// as it is and is no error; a failed build is reported with the form's name `what` (null: not
+// reported, the caller falls back).
+static int kern_build(mimic_vm *vm, const JitOpts &o, const char *what, JitKernel *k) {
+    JitKernel b;
+    const std::string src = mimic_jit_source(vm->h_dp, vm->h_all, o, &b.info);
+    if (o.spread && !(b.info.spread && b.info.spread_own == o.spread->own)) return 0;
+    if (o.proc && !b.info.proc_ok) return 0;
+    std::string log;
+    if (mimic_jit_compile(vm->s.device, src, &b.fn, &log))
+        return what ? fail(vm, MIMIC_EDEVICE, "JIT build failed%s: %s", what, log.c_str()) : MIMIC_EDEVICE;
+    b.state = 1;
+    *k = b;
+    return 0;
+}
+
 // The spread kernel of the VM's xdp_md programs (jit.cpp analyze_spread), built once per program
 // set: the VM's per-CPU arrays whose values the arena keeps 8-byte aligned are the candidates; the
 // analysis names the one map the programs count into, and the kernel is then generated with an
@@ -1916,40 +1953,28 @@ static uint32_t spread_ppb() {
     }();
     return v;
 }
-static int spread_build(mimic_vm *vm) {
-    if (vm->spread_state) return 0;
-    vm->spread_state = -1;
-    SpreadReq req;
-    req.ppb = spread_ppb();
-    for (size_t s = 0; s < vm->h_all.size(); s++) {
-        const DInsn &x = vm->h_all[s];
-        const uint32_t mh = AUX_MAPHINT(x.aux);
-        if (AUX_H(x.aux) != H_LDIMM || !mh || mh > vm->maps.size()) continue;
-        const HostMap &hm = vm->maps[mh - 1];
-        const DMap dm = to_dmap(hm);
-        if (hm.family != FAM_PERCPU_ARRAY || (dm.dev_off & 7) || (dm.dev_stride & 7)) continue;
-        req.slot_map[(uint32_t)s] = mh - 1;
-        req.shape[mh - 1] = {hm.max_entries * hm.value_size, hm.value_size};
-    }
+// own ("spread_build_own" in jit.py and the tests): the owned form (jit.cpp, SpreadReq::own); its
+// LDS table holds up to 256 rows of the counted map's row (32 KiB at most), so a batch with P
+// packets per vCPU can use it when 256 / P rows fit.
+static int spread_build(mimic_vm *vm, bool own) {
+    JitKernel &k = vm->kern[own ? K_OWN : K_SPREAD];
+    if (k.state) return 0;
+    k.state = -1;
+    PercpuSlots ps = percpu_slots(vm);
+    SpreadReq &req = ps.seed;
     if (req.slot_map.empty()) return 0;
-    JitInfo info{};
-    std::string src = mimic_jit_source(vm->h_dp, vm->h_all, CTX_XDP, &info, nullptr, false, &req);
-    if (!info.spread) return 0;
-    // the counted map and its row: an LDS table of min(ppb, V) rows when that fits 32 KiB
-    uint32_t row = 0;
-    for (auto &kv : req.shape) row = std::max(row, kv.second.first);
-    const uint64_t rows = std::min<uint64_t>(req.ppb, (uint64_t)vm->s.vcpu_count);
-    if (rows * row <= 32768) {
-        req.lds_rows = (uint32_t)rows;
-        src = mimic_jit_source(vm->h_dp, vm->h_all, CTX_XDP, &info, nullptr, false, &req);
+    req.own = own;
+    if (own) {
+        req.lds_rows = ps.row ? std::min<uint32_t>(256u, 32768u / ps.row) : 0u;
+        if (req.lds_rows < 2) return 0;
+    } else {   // an LDS table of min(ppb, V) rows of the longest row when that fits 32 KiB
+        req.ppb = spread_ppb();
+        const uint64_t rows = std::min<uint64_t>(req.ppb, (uint64_t)vm->s.vcpu_count);
+        if (rows * ps.row <= 32768) req.lds_rows = (uint32_t)rows;
     }
-    vm->spread_lds = req.lds_rows > 0;
-    std::string log;
-    if (mimic_jit_compile(vm->s.device, src, &vm->jit_fn_spread, &log))
-        return fail(vm, MIMIC_EDEVICE, "JIT build failed (spread kernel): %s", log.c_str());
-    vm->jit_info_spread = info;
-    vm->spread_state = 1;
-    return 0;
+    JitOpts o;
+    o.spread = &req;
+    return kern_build(vm, o, own ? " (owned spread kernel)" : " (spread kernel)", &k);
 }
 
 // lanes the one-lane JIT kernel holds resident at its 4-wave budget: CUs x 4 SIMDs x 4 waves x 64
@@ -1960,42 +1985,6 @@ static uint32_t chip_lanes(mimic_vm *vm) {
         cus = hipGetDeviceProperties(&pr, vm->s.device) == hipSuccess && pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256;
     }
     return (uint32_t)cus * 4u * 4u * 64u;
-}
-
-// The owned form (jit.cpp, SpreadReq::own): built once per program set when the programs allow a
-// spread kernel; its LDS table holds up to 256 rows of the counted map's row (32 KiB at most), so a
-// batch with P packets per vCPU can use it when 256 / P rows fit.
-static int spread_build_own(mimic_vm *vm) {
-    if (vm->spread_own_state) return 0;
-    vm->spread_own_state = -1;
-    SpreadReq req;
-    req.own = true;
-    for (size_t s = 0; s < vm->h_all.size(); s++) {
-        const DInsn &x = vm->h_all[s];
-        const uint32_t mh = AUX_MAPHINT(x.aux);
-        if (AUX_H(x.aux) != H_LDIMM || !mh || mh > vm->maps.size()) continue;
-        const HostMap &hm = vm->maps[mh - 1];
-        const DMap dm = to_dmap(hm);
-        if (hm.family != FAM_PERCPU_ARRAY || (dm.dev_off & 7) || (dm.dev_stride & 7)) continue;
-        req.slot_map[(uint32_t)s] = mh - 1;
-        req.shape[mh - 1] = {hm.max_entries * hm.value_size, hm.value_size};
-    }
-    if (req.slot_map.empty()) return 0;
-    uint32_t row = 0;
-    for (auto &kv : req.shape) row = std::max(row, kv.second.first);
-    if (!row) return 0;
-    req.lds_rows = std::min<uint32_t>(256u, 32768u / row);
-    if (req.lds_rows < 2) return 0;
-    JitInfo info{};
-    const std::string src = mimic_jit_source(vm->h_dp, vm->h_all, CTX_XDP, &info, nullptr, false, &req);
-    if (!info.spread || !info.spread_own) return 0;
-    std::string log;
-    if (mimic_jit_compile(vm->s.device, src, &vm->jit_fn_spread_own, &log))
-        return fail(vm, MIMIC_EDEVICE, "JIT build failed (owned spread kernel): %s", log.c_str());
-    vm->jit_info_spread_own = info;
-    vm->spread_own_rows = req.lds_rows;
-    vm->spread_own_state = 1;
-    return 0;
 }
 
 // The VM's private memory for `lanes` lanes of q_per_lane qwords, qword-interleaved with stride
@@ -2036,17 +2025,113 @@ static int spread_check(mimic_vm *vm) {
     return 0;
 }
 
-// LD_IMM64 slots naming a per-CPU array whose row the lane value cache can hold, with its E * S
-static std::vector<std::pair<uint32_t, uint32_t>> vc_slots_of(const mimic_vm *vm) {
-    std::vector<std::pair<uint32_t, uint32_t>> vc;
-    for (size_t s = 0; s < vm->h_all.size(); s++) {
-        const DInsn &x = vm->h_all[s];
-        const uint32_t mh = AUX_MAPHINT(x.aux);
-        if (AUX_H(x.aux) != H_LDIMM || !mh || mh > vm->maps.size()) continue;
-        const HostMap &hm = vm->maps[mh - 1];
-        if (vc_row_ok(hm.family, hm.max_entries, hm.value_size)) vc.push_back({(uint32_t)s, hm.max_entries * hm.value_size});
+// the per-lane step counters (KParams::lane_steps) for a launch of `lanes` lanes, in whole blocks
+static int lane_steps_ensure(mimic_vm *vm, uint32_t lanes, hipStream_t st) {
+    if (lanes <= vm->lane_steps_cap) return 0;
+    const uint32_t cap = (lanes + 255) & ~255u;
+    hipStreamSynchronize(st);
+    hipFree(vm->d_lane_steps);
+    vm->d_lane_steps = nullptr;
+    HIP_OK(vm, hipMalloc(&vm->d_lane_steps, (uint64_t)cap * sizeof(uint64_t)));
+    vm->lane_steps_cap = cap;
+    return 0;
+}
+
+// The kernel one batch runs on: jit false = the interpreter; else vm->kern[form], built here on
+// first use (spread / own: a spread launch, in its owned form).  kp: the launch parameters as far
+// as they are known (budget, per_lane, cancel_any ...); an owned launch's kp->own_q is set here.
+struct KernChoice {
+    int form;
+    bool jit, spread, own;
+};
+static int kern_choose(mimic_vm *vm, uint32_t ctx, const mimic_xdp_batch *b, bool step, bool skb, bool proc_jit,
+                       uint32_t cpu_lanes, KParams *kp, KernChoice *out) {
+    int rc;
+    // stepping runs on the interpreter; a Run the engine chose for the single-process JIT form
+    // (process_advance) on that form
+    bool jit = vm->exec_mode == MIMIC_EXEC_JIT && (!step || proc_jit);
+    JitKernel &lane = vm->kern[K_LANE + ctx];
+    if (jit && !proc_jit && !lane.state) {
+        const std::vector<std::pair<uint32_t, uint32_t>> vc = percpu_slots(vm).vc;
+        JitOpts o;
+        o.ctx_kind = ctx;
+        o.vc_slots = &vc;
+        if ((rc = kern_build(vm, o, "", &lane))) return rc;
+        // A small kernel is built for 4 waves per SIMD (jit.cpp); when that spills, the form
+        // without early packet loads (whose values are what stays live) may not: keep the one
+        // with less scratch.  cfg 4: 0.136 -> 0.128 ms per launch.
+        int ls0 = 0, ls1 = 0;
+        if (lane.info.early_loads && lane.info.cold_inline &&
+            hipFuncGetAttribute(&ls0, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, lane.fn) == hipSuccess && ls0 > 0) {
+            JitKernel alt;
+            o.no_early_loads = true;
+            if (!kern_build(vm, o, nullptr, &alt) &&
+                hipFuncGetAttribute(&ls1, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, alt.fn) == hipSuccess && ls1 < ls0)
+                lane = alt;
+        }
     }
-    return vc;
+    if (jit && !proc_jit) {  // a loop-free kernel has no budget checks: tiny budgets run on the interpreter
+        const uint64_t bound = mimic_jit_step_bound(lane.info, kp->max_tail_calls);
+        if (bound && kp->budget < bound) jit = false;
+    }
+    // Spread launch (jit.cpp analyze_spread): a vCPU's packets on many lanes, for batches where
+    // every vCPU has many packets (the one-lane-per-vCPU kernel would run them as one serial chain
+    // per lane, e.g. V = runtime.NumCPU(), vm.go:64).  MIMIC_SPREAD=0: never; =1: whenever the
+    // program set allows it; default: when n >= 8 V.
+    bool spread = false, own = false;
+    if (jit && !step && !skb && b->n > 0 && (b->schedule == MIMIC_SCHED_CHUNKED || b->schedule == MIMIC_SCHED_INTERLEAVED)) {
+        const char *sv = getenv("MIMIC_SPREAD");
+        const int knob = vm->spread_mode >= 0 ? vm->spread_mode : sv && *sv ? atoi(sv) : -1;
+        // the owned form, for batches of 2..256 packets per vCPU (Q packets per thread, below): by
+        // default whenever the programs and the table allow it -- classifier at V = 262 144 (cfg 2)
+        // 25.0 vs 25.7 us, parse5 at V = 262 144 (cfg 3) 0.74 vs 1.03 ms, V = 16 384 with 64 packets
+        // per vCPU 2x the table spread (profiles/r05/).  MIMIC_SPREAD_OWN=0: never.
+        const char *ov = getenv("MIMIC_SPREAD_OWN");
+        const bool own_pref = !(ov && ov[0] == '0');
+        if (knob != 0 && own_pref && kp->per_lane >= 2 && kp->per_lane <= 256) {
+            if ((rc = spread_build(vm, true))) return rc;
+            const JitKernel &ko = vm->kern[K_OWN];
+            // Q packets per thread: enough threads to fill the chip about once (fewer, longer threads
+            // measured faster: V = 131 072, P = 4: 17.6 us at Q = 1, 15.5 at Q = 2), a divisor of P
+            // whose 256 Q / P rows fit the table (MIMIC_SPREAD_OWN_Q: a fixed Q, measurement)
+            const uint32_t P = kp->per_lane, cl = chip_lanes(vm), rows = ko.info.spread_rows;
+            const char *qv = getenv("MIMIC_SPREAD_OWN_Q");
+            uint32_t q = qv && *qv ? (uint32_t)atoi(qv) : (uint32_t)std::max<uint64_t>(1, ((uint64_t)b->n + cl - 1) / cl);
+            q = std::max<uint32_t>(1, std::min(q, P));
+            while (q > 1 && (P % q || 256u * q / P > rows)) q--;
+            kp->own_q = q;
+            own = ko.state > 0 && P % q == 0 && 256u * q / P <= rows && 256u * q / P >= 1u &&
+                  mimic_jit_step_bound(ko.info, kp->max_tail_calls) <= kp->budget;
+            spread = own;
+        }
+        if (!own && (knob == 1 || (knob != 0 && (uint64_t)b->n >= 8ull * cpu_lanes))) {
+            if ((rc = spread_build(vm, false))) return rc;
+            const JitKernel &ks = vm->kern[K_SPREAD];
+            spread = ks.state > 0 && mimic_jit_step_bound(ks.info, kp->max_tail_calls) <= kp->budget;
+            // without the LDS table every increment is a scattered agent-scope atomic: worth it only
+            // when the one-lane-per-vCPU kernel has few lanes
+            if (knob != 1 && !ks.info.spread_rows && cpu_lanes > 16384) spread = false;
+        }
+    }
+    // a launch given contexts runs the variant with the per-packet Run(ctx) check, one lane per vCPU
+    const bool cxk = jit && kp->cancel_any;
+    if (cxk) {
+        spread = own = false;
+        if (!vm->kern[K_CX + ctx].state) {
+            const std::vector<std::pair<uint32_t, uint32_t>> vc = percpu_slots(vm).vc;
+            JitOpts o;
+            o.ctx_kind = ctx;
+            o.vc_slots = &vc;
+            o.no_early_loads = !lane.info.early_loads;   // as the VM's own kernel (the spill choice above)
+            o.ctx_check = true;
+            if ((rc = kern_build(vm, o, "", &vm->kern[K_CX + ctx]))) return rc;
+        }
+    }
+    *out = KernChoice{proc_jit ? K_PROC : own ? K_OWN : spread ? K_SPREAD : cxk ? K_CX + (int)ctx : K_LANE + (int)ctx,
+                      jit, spread, own};
+    const JitKernel &k = vm->kern[out->form];
+    if (proc_jit && (!k.fn || !k.info.proc_ok)) return fail(vm, MIMIC_EDEVICE, "process: no single-process JIT kernel (engine)");
+    return 0;
 }
 
 static int run_xdp_impl(mimic_vm *vm, uint32_t prog_id, const mimic_xdp_batch *b, const mimic_xdp_results *res,
@@ -2092,13 +2177,7 @@ static int run_xdp_impl(mimic_vm *vm, uint32_t prog_id, const mimic_xdp_batch *b
         rc = priv_ensure(vm, q_per_lane, plan, st);
         if (rc) return rc;
     }
-    if (lanes > vm->lane_steps_cap) {
-        hipStreamSynchronize(st);
-        hipFree(vm->d_lane_steps);
-        vm->d_lane_steps = nullptr;
-        HIP_OK(vm, hipMalloc(&vm->d_lane_steps, (uint64_t)plan * sizeof(uint64_t)));
-        vm->lane_steps_cap = plan;
-    }
+    if ((rc = lane_steps_ensure(vm, lanes, st))) return rc;
     KParams kp{};
     kp.insns = vm->d_insns;
     kp.progs = vm->d_progs;
@@ -2238,95 +2317,11 @@ static int run_xdp_impl(mimic_vm *vm, uint32_t prog_id, const mimic_xdp_batch *b
     default:
         return fail(vm, MIMIC_EINVAL, "unknown schedule %u", b->schedule);
     }
-    // stepping runs on the interpreter; a Run the engine chose for the single-process JIT form
-    // (process_advance) on that form
-    bool jit = vm->exec_mode == MIMIC_EXEC_JIT && (!step || proc_jit);
-    if (jit && !proc_jit && !vm->jit_fn[ctx]) {
-        std::string log;
-        const std::vector<std::pair<uint32_t, uint32_t>> vc = vc_slots_of(vm);
-        if (mimic_jit_compile(vm->s.device, mimic_jit_source(vm->h_dp, vm->h_all, ctx, &vm->jit_info[ctx], &vc),
-                              &vm->jit_fn[ctx], &log))
-            return fail(vm, MIMIC_EDEVICE, "JIT build failed: %s", log.c_str());
-        // A small kernel is built for 4 waves per SIMD (jit.cpp); when that spills, the form
-        // without early packet loads (whose values are what stays live) may not: keep the one
-        // with less scratch.  cfg 4: 0.136 -> 0.128 ms per launch.
-        const JitInfo &j0 = vm->jit_info[ctx];
-        int ls0 = 0;
-        if (j0.early_loads && j0.cold_inline &&
-            hipFuncGetAttribute(&ls0, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, vm->jit_fn[ctx]) == hipSuccess && ls0 > 0) {
-            JitInfo j1;
-            hipFunction_t f1 = nullptr;
-            int ls1 = 0;
-            if (!mimic_jit_compile(vm->s.device, mimic_jit_source(vm->h_dp, vm->h_all, ctx, &j1, &vc, true), &f1, &log) &&
-                hipFuncGetAttribute(&ls1, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, f1) == hipSuccess && ls1 < ls0) {
-                vm->jit_fn[ctx] = f1;
-                vm->jit_info[ctx] = j1;
-            }
-        }
-    }
-    if (jit && !proc_jit) {  // a loop-free kernel has no budget checks: tiny budgets run on the interpreter
-        const uint64_t bound = mimic_jit_step_bound(vm->jit_info[ctx], kp.max_tail_calls);
-        if (bound && kp.budget < bound) jit = false;
-    }
-    // Spread launch (jit.cpp analyze_spread): a vCPU's packets on many lanes, for batches where
-    // every vCPU has many packets (the one-lane-per-vCPU kernel would run them as one serial chain
-    // per lane, e.g. V = runtime.NumCPU(), vm.go:64).  MIMIC_SPREAD=0: never; =1: whenever the
-    // program set allows it; default: when n >= 8 V.
-    bool spread = false, own = false;
-    if (jit && !step && !skb && b->n > 0 && (b->schedule == MIMIC_SCHED_CHUNKED || b->schedule == MIMIC_SCHED_INTERLEAVED)) {
-        const char *sv = getenv("MIMIC_SPREAD");
-        const int knob = vm->spread_mode >= 0 ? vm->spread_mode : sv && *sv ? atoi(sv) : -1;
-        // the owned form, for batches of 2..256 packets per vCPU (Q packets per thread, below): by
-        // default whenever the programs and the table allow it -- classifier at V = 262 144 (cfg 2)
-        // 25.0 vs 25.7 us, parse5 at V = 262 144 (cfg 3) 0.74 vs 1.03 ms, V = 16 384 with 64 packets
-        // per vCPU 2x the table spread (profiles/r05/).  MIMIC_SPREAD_OWN=0: never.
-        const char *ov = getenv("MIMIC_SPREAD_OWN");
-        const bool own_pref = !(ov && ov[0] == '0');
-        if (knob != 0 && own_pref && kp.per_lane >= 2 && kp.per_lane <= 256) {
-            rc = spread_build_own(vm);
-            if (rc) return rc;
-            // Q packets per thread: enough threads to fill the chip about once (fewer, longer threads
-            // measured faster: V = 131 072, P = 4: 17.6 us at Q = 1, 15.5 at Q = 2), a divisor of P
-            // whose 256 Q / P rows fit the table (MIMIC_SPREAD_OWN_Q: a fixed Q, measurement)
-            const uint32_t P = kp.per_lane, cl = chip_lanes(vm);
-            const char *qv = getenv("MIMIC_SPREAD_OWN_Q");
-            uint32_t q = qv && *qv ? (uint32_t)atoi(qv) : (uint32_t)std::max<uint64_t>(1, ((uint64_t)b->n + cl - 1) / cl);
-            q = std::max<uint32_t>(1, std::min(q, P));
-            while (q > 1 && (P % q || 256u * q / P > vm->spread_own_rows)) q--;
-            kp.own_q = q;
-            own = vm->spread_own_state > 0 && P % q == 0 && 256u * q / P <= vm->spread_own_rows && 256u * q / P >= 1u &&
-                  mimic_jit_step_bound(vm->jit_info_spread_own, kp.max_tail_calls) <= kp.budget;
-            spread = own;
-        }
-        if (!own && (knob == 1 || (knob != 0 && (uint64_t)b->n >= 8ull * cpu_lanes))) {
-            rc = spread_build(vm);
-            if (rc) return rc;
-            spread = vm->spread_state > 0 && mimic_jit_step_bound(vm->jit_info_spread, kp.max_tail_calls) <= kp.budget;
-            // without the LDS table every increment is a scattered agent-scope atomic: worth it only
-            // when the one-lane-per-vCPU kernel has few lanes
-            if (knob != 1 && !vm->spread_lds && cpu_lanes > 16384) spread = false;
-        }
-    }
-    // a launch given contexts runs the variant with the per-packet Run(ctx) check, one lane per vCPU
-    const bool cxk = jit && kp.cancel_any;
-    if (cxk) {
-        spread = own = false;
-        if (!vm->jit_fn_cx[ctx]) {
-            const std::vector<std::pair<uint32_t, uint32_t>> vc = vc_slots_of(vm);
-            std::string log;
-            // with or without early packet loads as the VM's own kernel (the spill choice above)
-            if (mimic_jit_compile(vm->s.device,
-                                  mimic_jit_source(vm->h_dp, vm->h_all, ctx, &vm->jit_info_cx[ctx], &vc,
-                                                   !vm->jit_info[ctx].early_loads, nullptr, true),
-                                  &vm->jit_fn_cx[ctx], &log))
-                return fail(vm, MIMIC_EDEVICE, "JIT build failed: %s", log.c_str());
-        }
-    }
-    const JitInfo &ji = proc_jit ? vm->jit_info_proc : own ? vm->jit_info_spread_own : spread ? vm->jit_info_spread
-                        : cxk ? vm->jit_info_cx[ctx] : vm->jit_info[ctx];
-    hipFunction_t jfn = proc_jit ? vm->jit_fn_proc : own ? vm->jit_fn_spread_own : spread ? vm->jit_fn_spread
-                        : cxk ? vm->jit_fn_cx[ctx] : vm->jit_fn[ctx];
-    if (proc_jit && (!jfn || !ji.proc_ok)) return fail(vm, MIMIC_EDEVICE, "process: no single-process JIT kernel (engine)");
+    KernChoice kc;
+    if ((rc = kern_choose(vm, ctx, b, step != nullptr, skb != nullptr, proc_jit, cpu_lanes, &kp, &kc))) return rc;
+    const bool jit = kc.jit, spread = kc.spread, own = kc.own;
+    const JitKernel &kern = vm->kern[kc.form];
+    const JitInfo &ji = kern.info;
     uint32_t run_lanes = lanes;
     if (spread) {
         // owned: 256 / P vCPU lanes per block
@@ -2336,13 +2331,7 @@ static int run_xdp_impl(mimic_vm *vm, uint32_t prog_id, const mimic_xdp_batch *b
         run_lanes = blocks * 256u;
         rc = priv_ensure(vm, q_per_lane, run_lanes, st);   // private memory (stack ...) per spread lane
         if (rc) return rc;
-        if (run_lanes > vm->lane_steps_cap) {
-            hipStreamSynchronize(st);
-            hipFree(vm->d_lane_steps);
-            vm->d_lane_steps = nullptr;
-            HIP_OK(vm, hipMalloc(&vm->d_lane_steps, (uint64_t)run_lanes * sizeof(uint64_t)));
-            vm->lane_steps_cap = run_lanes;
-        }
+        if ((rc = lane_steps_ensure(vm, run_lanes, st))) return rc;
         if (!vm->d_spread_bad) {
             HIP_OK(vm, hipMalloc(&vm->d_spread_bad, 64));
             HIP_OK(vm, hipMemset(vm->d_spread_bad, 0, 64));
@@ -2466,7 +2455,7 @@ static int run_xdp_impl(mimic_vm *vm, uint32_t prog_id, const mimic_xdp_batch *b
         }
     }
     if (jit) {  // launch parameters by value: the runtime copies them into the kernarg segment
-        if (mimic_jit_launch(jfn, &kp, st))
+        if (mimic_jit_launch(kern.fn, &kp, st))
             return fail(vm, MIMIC_EDEVICE, "launch: %s", hipGetErrorString(hipGetLastError()));
         // the interpreter finishes what the kernel deferred (a wave without a deferred lane returns at once)
         if (ji.defer && mimic_launch_xdp_resume(&kp, st))
@@ -2653,20 +2642,16 @@ static void process_regs(const mimic_process *p, mimic_process_regs *out) {
 // Process.Run tiering (mimic_vm::proc_jit_after): the program set's single-process JIT form, built
 // once per program set; false when it is not usable (then Runs stay on the interpreter)
 static bool proc_jit_ready(mimic_vm *vm) {
-    if (vm->proc_jit == 0) {
-        vm->proc_jit = -1;
-        const std::vector<std::pair<uint32_t, uint32_t>> vc = vc_slots_of(vm);
-        std::string log;
-        JitInfo ji{};
-        hipFunction_t fn = nullptr;
-        const std::string src = mimic_jit_source(vm->h_dp, vm->h_all, CTX_XDP, &ji, &vc, false, nullptr, false, true);
-        if (ji.proc_ok && !mimic_jit_compile(vm->s.device, src, &fn, &log)) {
-            vm->jit_fn_proc = fn;
-            vm->jit_info_proc = ji;
-            vm->proc_jit = 1;
-        }
+    JitKernel &k = vm->kern[K_PROC];
+    if (k.state == 0) {
+        k.state = -1;
+        const std::vector<std::pair<uint32_t, uint32_t>> vc = percpu_slots(vm).vc;
+        JitOpts o;
+        o.vc_slots = &vc;
+        o.proc = true;
+        kern_build(vm, o, nullptr, &k);   // (a failed build is not reported: Runs stay on the interpreter)
     }
-    return vm->proc_jit > 0;
+    return k.state > 0;
 }
 // a Run (not a Step) of a process that has not started, on one of this engine's vCPUs, with a
 // budget the loop-free form cannot exceed, once the VM has made enough Runs
@@ -2675,7 +2660,7 @@ static bool proc_jit_use(mimic_process *p, uint64_t budget) {
     if (vm->exec_mode != MIMIC_EXEC_JIT || vm->proc_jit_after < 0 || p->skb || p->h.started) return false;
     if (p->cpu < vm->s.vcpu_begin || p->cpu >= vm->s.vcpu_begin + vm->s.vcpu_count) return false;
     if (vm->proc_runs++ < (uint64_t)vm->proc_jit_after || !proc_jit_ready(vm)) return false;
-    const uint64_t bound = mimic_jit_step_bound(vm->jit_info_proc, (uint32_t)std::max(0, vm->s.max_tail_calls));
+    const uint64_t bound = mimic_jit_step_bound(vm->kern[K_PROC].info, (uint32_t)std::max(0, vm->s.max_tail_calls));
     return bound && bound <= budget;
 }
 
@@ -3193,6 +3178,19 @@ int mimic_set_spread(mimic_vm *vm, int32_t mode) {
 }
 int mimic_last_exec(const mimic_vm *vm) { return vm ? vm->last_exec : MIMIC_EINVAL; }
 
+// raw programs (slots as mimic_program_load takes them) -> the JIT's input tables; false when one
+// does not decode
+static bool decode_raw_programs(const void *const *progs, const uint32_t *n_slots, uint32_t n_progs,
+                                std::vector<DInsn> &all, std::vector<DProg> &dp) {
+    std::vector<HostProg> hp(n_progs);
+    for (uint32_t p = 0; p < n_progs; p++) {
+        std::string err;
+        if (decode_program((const uint8_t *)progs[p], n_slots[p], hp[p].ins, &err)) return false;
+    }
+    build_host_tables(hp, all, dp);
+    return true;
+}
+
 // The JIT kernel source for a set of raw programs (slots as mimic_program_load takes them; map
 // relocations do not change the code shape).  Returns the source length; copies it if it fits.
 // Host only: no device needed.
@@ -3213,21 +3211,21 @@ long mimic_jit_source_vc(const void *const *progs, const uint32_t *n_slots, uint
     ctx_kind &= 0xff;
     if (ctx_kind != MIMIC_CTX_XDP && ctx_kind != MIMIC_CTX_SKB) return MIMIC_EINVAL;
     if (proc && ctx_kind != MIMIC_CTX_XDP) return MIMIC_EINVAL;
-    std::vector<HostProg> hp(n_progs);
-    for (uint32_t p = 0; p < n_progs; p++) {
-        std::string err;
-        if (decode_program((const uint8_t *)progs[p], n_slots[p], hp[p].ins, &err)) return MIMIC_EINVAL;
-    }
     std::vector<DInsn> all;
     std::vector<DProg> dp;
-    build_host_tables(hp, all, dp);
+    if (!decode_raw_programs(progs, n_slots, n_progs, all, dp)) return MIMIC_EINVAL;
     std::vector<std::pair<uint32_t, uint32_t>> vc;
     for (uint32_t q = 0; q < n_vc; q++) {
         const uint32_t p = vc_slots[3 * q], s = vc_slots[3 * q + 1], rb = vc_slots[3 * q + 2];
         if (p >= dp.size() || s >= dp[p].n) return MIMIC_EINVAL;
         vc.push_back({dp[p].base + s, rb});
     }
-    const std::string src = mimic_jit_source(dp, all, (uint32_t)ctx_kind, nullptr, &vc, no_early_loads, nullptr, false, proc);
+    JitOpts o;
+    o.ctx_kind = (uint32_t)ctx_kind;
+    o.vc_slots = &vc;
+    o.no_early_loads = no_early_loads;
+    o.proc = proc;
+    const std::string src = mimic_jit_source(dp, all, o, nullptr);
     if (buf && cap > src.size()) memcpy(buf, src.c_str(), src.size() + 1);
     return (long)src.size();
 }
@@ -3239,14 +3237,9 @@ long mimic_jit_source_vc(const void *const *progs, const uint32_t *n_slots, uint
 long mimic_jit_source_spread(const void *const *progs, const uint32_t *n_slots, uint32_t n_progs, const uint32_t *pc,
                              uint32_t n_pc, const uint32_t *shapes, uint32_t n_shapes, uint32_t lds_rows,
                              int32_t *spread_out, char *buf, size_t cap) {
-    std::vector<HostProg> hp(n_progs);
-    for (uint32_t p = 0; p < n_progs; p++) {
-        std::string err;
-        if (decode_program((const uint8_t *)progs[p], n_slots[p], hp[p].ins, &err)) return MIMIC_EINVAL;
-    }
     std::vector<DInsn> all;
     std::vector<DProg> dp;
-    build_host_tables(hp, all, dp);
+    if (!decode_raw_programs(progs, n_slots, n_progs, all, dp)) return MIMIC_EINVAL;
     SpreadReq req;
     for (uint32_t q = 0; q < n_pc; q++) {
         const uint32_t p = pc[3 * q], sl = pc[3 * q + 1];
@@ -3255,9 +3248,11 @@ long mimic_jit_source_spread(const void *const *progs, const uint32_t *n_slots, 
     }
     for (uint32_t q = 0; q < n_shapes; q++) req.shape[shapes[3 * q]] = {shapes[3 * q + 1], shapes[3 * q + 2]};
     req.lds_rows = lds_rows & 0x7fffffffu;
-    req.own = (lds_rows >> 31) != 0;   // bit 31: the owned form (spread_build_own)
+    req.own = (lds_rows >> 31) != 0;   // bit 31: the owned form (spread_build own)
+    JitOpts o;
+    o.spread = &req;
     JitInfo info{};
-    const std::string src = mimic_jit_source(dp, all, MIMIC_CTX_XDP, &info, nullptr, false, &req);
+    const std::string src = mimic_jit_source(dp, all, o, &info);
     if (spread_out) *spread_out = info.spread ? 1 : 0;
     if (buf && cap > src.size()) memcpy(buf, src.c_str(), src.size() + 1);
     return (long)src.size();
@@ -3271,16 +3266,13 @@ int mimic_jit_prebuild(const void *const *progs, const uint32_t *n_slots, uint32
 
 int mimic_jit_prebuild_ctx(const void *const *progs, const uint32_t *n_slots, uint32_t n_progs, int32_t ctx_kind) {
     if (ctx_kind != MIMIC_CTX_XDP && ctx_kind != MIMIC_CTX_SKB) return MIMIC_EINVAL;
-    std::vector<HostProg> hp(n_progs);
-    for (uint32_t p = 0; p < n_progs; p++) {
-        std::string err;
-        if (decode_program((const uint8_t *)progs[p], n_slots[p], hp[p].ins, &err)) return MIMIC_EINVAL;
-    }
     std::vector<DInsn> all;
     std::vector<DProg> dp;
-    build_host_tables(hp, all, dp);
+    if (!decode_raw_programs(progs, n_slots, n_progs, all, dp)) return MIMIC_EINVAL;
+    JitOpts o;
+    o.ctx_kind = (uint32_t)ctx_kind;
     std::string log;
-    return mimic_jit_prebuild_source(mimic_jit_source(dp, all, (uint32_t)ctx_kind, nullptr), &log) ? MIMIC_EINVAL : 0;
+    return mimic_jit_prebuild_source(mimic_jit_source(dp, all, o, nullptr), &log) ? MIMIC_EINVAL : 0;
 }
 
 // hipRTC-compile a JIT source for gfx950 without loading it (host only).  0 = ok; the compiler

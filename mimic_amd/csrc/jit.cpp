@@ -2399,22 +2399,21 @@ std::map<CacheKey, hipFunction_t> g_cache;
 
 }  // namespace
 
-std::string mimic_jit_source(const std::vector<DProg> &progs, const std::vector<DInsn> &all, uint32_t ctx_kind,
-                             JitInfo *info, const std::vector<std::pair<uint32_t, uint32_t>> *vc_slots, bool no_early_loads,
-                             const SpreadReq *spread, bool ctx_check, bool proc) {
+std::string mimic_jit_source(const std::vector<DProg> &progs, const std::vector<DInsn> &all, const JitOpts &o,
+                             JitInfo *info) {
     std::vector<ProgView> v;
     for (size_t p = 0; p < progs.size(); p++) v.push_back(ProgView{(uint32_t)p, progs[p].n, progs[p].base, all.data() + progs[p].base});
-    Gen g(v, ctx_kind);
-    if (vc_slots)
-        for (auto &v : *vc_slots)
+    Gen g(v, o.ctx_kind);
+    if (o.vc_slots)
+        for (auto &v : *o.vc_slots)
             if (v.second > 0 && v.second <= MIMIC_VC_MAX_ROW && !(v.second & 7)) g.vc_ok[v.first] = v.second;
-    if (no_early_loads) g.speculate = 0;
-    g.spread_req = spread;
+    if (o.no_early_loads) g.speculate = 0;
+    g.spread_req = o.spread;
     // (MIMIC_JIT_CTXCHECK=1: the context variant from every entry point -- CPU compile tests)
     static const bool ctx_env = getenv("MIMIC_JIT_CTXCHECK") && getenv("MIMIC_JIT_CTXCHECK")[0] == '1';
-    g.ctx_check = ctx_check || ctx_env;
-    g.proc = proc;
-    if (proc) g.inc_knob = false;
+    g.ctx_check = o.ctx_check || ctx_env;
+    g.proc = o.proc;
+    if (o.proc) g.inc_knob = false;
     std::string src = g.source();
     if (info) {
         info->checks_budget = g.careful_copies;
@@ -2427,12 +2426,12 @@ std::string mimic_jit_source(const std::vector<DProg> &progs, const std::vector<
         info->spread_own = g.spread_own;
         info->hash_combine = g.hash_combine;
         info->hash_chunk = g.hash_chunk;
-        info->proc = proc;
-        info->proc_ok = proc && ctx_kind == CTX_XDP && !g.careful_copies && !g.defer_mode && !g.spread_on && !g.census;
+        info->proc = o.proc;
+        info->proc_ok = o.proc && o.ctx_kind == CTX_XDP && !g.careful_copies && !g.defer_mode && !g.spread_on && !g.census;
         info->spread_map = g.spread_map;
         info->spread_n = g.spread_n;
         info->spread_roww = g.spread_n ? g.spread_row / g.spread_n : 0;
-        info->spread_rows = g.spread_on && spread ? spread->lds_rows : 0;
+        info->spread_rows = g.spread_on && o.spread ? o.spread->lds_rows : 0;
     }
     return src;
 }

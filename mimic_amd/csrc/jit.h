@@ -37,17 +37,21 @@ struct SpreadReq {
     // (2 <= P <= 256), its counters into an LDS table it then adds into the rows it alone owns
     bool own = false;
 };
-// ctx_kind: CtxKind of the batches the kernel runs
-// ctx_check: the variant for launches given Run(ctx) contexts (KParams::cancel_any)
-// proc: the single-process form for Process.Run (JitInfo::proc)
-// vc_slots: (kernel-wide index, E * S) of the LD_IMM64 slots whose constant is the object of a
-// per-CPU array whose row the lane value cache may hold: E * S a multiple of 8, at most
-// MIMIC_VC_MAX_ROW bytes (rows up to 32 bytes in registers, longer ones in LDS)
 #define MIMIC_VC_MAX_ROW 128u
-std::string mimic_jit_source(const std::vector<DProg> &progs, const std::vector<DInsn> &all, uint32_t ctx_kind,
-                             JitInfo *info, const std::vector<std::pair<uint32_t, uint32_t>> *vc_slots = nullptr,
-                             bool no_early_loads = false,
-                             const SpreadReq *spread = nullptr, bool ctx_check = false, bool proc = false);
+// Which kernel of a program set mimic_jit_source generates (the defaults: the one-lane xdp_md kernel)
+struct JitOpts {
+    uint32_t ctx_kind = CTX_XDP;   // CtxKind of the batches the kernel runs
+    // (kernel-wide index, E * S) of the LD_IMM64 slots whose constant is the object of a per-CPU
+    // array whose row the lane value cache may hold: E * S a multiple of 8, at most
+    // MIMIC_VC_MAX_ROW bytes (rows up to 32 bytes in registers, longer ones in LDS)
+    const std::vector<std::pair<uint32_t, uint32_t>> *vc_slots = nullptr;
+    bool no_early_loads = false;         // no packet loads issued early (analyze_spec)
+    const SpreadReq *spread = nullptr;   // a spread kernel, when the programs allow one
+    bool ctx_check = false;   // the variant for launches given Run(ctx) contexts (KParams::cancel_any)
+    bool proc = false;        // the single-process form for Process.Run (JitInfo::proc)
+};
+std::string mimic_jit_source(const std::vector<DProg> &progs, const std::vector<DInsn> &all, const JitOpts &o,
+                             JitInfo *info);
 // 0 when the kernel checks the budget itself; else the most steps one packet can take -- a
 // batch with a smaller budget must run on the interpreter
 uint64_t mimic_jit_step_bound(const JitInfo &info, uint32_t max_tail_calls);

@@ -15,9 +15,11 @@ import numpy as np
 import pytest
 
 import mimic_amd as M
-from harness import Scenario, build_engine, kernel_of, ncpus
+from harness import Scenario, build_engine, build_oracle, kernel_of, ncpus, spread_kernel_of
 from kat import jit_groups, load_cases, multi_cases, scenario
+from mimic_amd import asm as A
 from mimic_amd import workloads as W
+from test_gpu_spread import _counter_prog
 
 pytestmark = pytest.mark.gpu
 
@@ -32,12 +34,32 @@ def _wl(name):
     return Scenario(vcpus=64, maps=p.maps, progs=[(p.name, p.raw, p.relocs)])
 
 
+def _len_prog():
+    """_counter_prog(4) with another key and another verdict: per-CPU counter[(packet length + 1) & 3]
+    += 1, R0 = the packet's length (never _counter_prog's 2)."""
+    raw, rel = A.assemble([
+        A.mov64_reg(6, 1), A.ldx(4, 2, 6, 0), A.ldx(4, 3, 6, 4), A.mov64_reg(4, 3), A.alu64("sub", 4, 2, reg=True),
+        A.mov64_reg(8, 4), A.alu64("add", 4, 1), A.alu64("and", 4, 3), A.stx(4, 10, -4, 4), A.mov64_reg(2, 10),
+        A.alu64("add", 2, -4), A.ld_map_fd(1, "c"), A.call(A.FN_MAP_LOOKUP_ELEM), A.jmp("jeq", 0, 0, "out"),
+        A.ldx(4, 7, 0, 0), A.alu32("add", 7, 1), A.stx(4, 0, 0, 7), "out", A.mov64_reg(0, 8), A.exit_()])
+    return ("len4", raw, list(rel))
+
+
+def _reload_scs():
+    """test_kernels_rebuilt_after_a_program_load's VM before and after its AddProgram (V = 7)."""
+    p = _counter_prog(4)
+    one = Scenario(vcpus=7, maps=p.maps, progs=[(p.name, p.raw, p.relocs)])
+    return one, Scenario(vcpus=7, maps=p.maps, progs=one.progs + [_len_prog()])
+
+
 def jit_kernels():
-    scs = [sc for sc, _, _ in GROUPS] + [scenario(c) for c in MULTI] + [_wl(n) for n in PROGS]
+    scs = [sc for sc, _, _ in GROUPS] + [scenario(c) for c in MULTI] + [_wl(n) for n in PROGS] + list(_reload_scs())
     out = []
     for sc in scs:
         raws, ctx, vc = kernel_of(sc)
         out += [(raws, ctx, vc), (raws, ctx | 0x100, vc)]   # the batch kernel and the single-process form
+    for sc in _reload_scs():
+        out += [spread_kernel_of(sc), spread_kernel_of(sc, own=True)]
     return out
 
 
@@ -194,4 +216,60 @@ def test_processes_from_many_threads(gpu):
     assert not errs, errs[:3]
     assert got == [int(v) for v in np.asarray(want["r0"])]
     assert [bytes(maps[sc.maps[0]["name"]].Values(c)) for c in range(64)] == [bytes(v) for v in wmap]
+    vm.close()
+
+
+def test_kernels_rebuilt_after_a_program_load(gpu, monkeypatch):
+    """Every kernel form a VM keeps for its program set is built again after AddProgram: one VM
+    (V = 7) runs a batch on the owned spread kernel, the table spread kernel, the one-lane kernel,
+    its Run(ctx) variant and one Process.Run on the single-process form; then a second program is
+    loaded (another counter key, R0 = the packet's length: a kernel kept from the first program set
+    would get every packet wrong) and the same five run with it as entry.  Each run's R0 / status /
+    steps / err_pc and, after each, the per-CPU counters equal the oracle's running the same sequence."""
+    one, two = _reload_scs()
+    V = one.vcpus
+    vm, maps, pids = _engine(one, 0)
+    ovm, omids, opids = build_oracle(one)
+    live = M.WithCancel()
+    seed = [40]
+
+    def batch(pid, n, want, ctx=None):
+        seed[0] += 1
+        buf, off, lens = W.make_packets(n, sizes=(64, 65, 66, 67), weights=(1, 1, 1, 1), seed=seed[0])
+        o = ovm.run_xdp_batch(opids[pid], buf.copy(), off, lens, W.schedule_cpu(n, V, "chunked"))
+        b = M.XDPBatch.from_numpy(buf, off, lens, device="cuda:0", schedule=M.SCHED_CHUNKED)
+        e = vm.RunXDPBatch(pids[pid], b, ctx=ctx).numpy(n)
+        assert vm.LastExec() == want, (pid, n, want)
+        for k in ("r0", "status", "steps", "err_pc"):
+            assert np.array_equal(np.asarray(o[k]).astype(np.int64), np.asarray(e[k]).astype(np.int64)), (pid, want, k)
+        assert [maps["c"].Values(c) for c in range(V)] == [ovm.map_values(omids["c"], c) for c in range(V)], (pid, want)
+        return lens, np.asarray(e["r0"]).astype(np.int64)
+
+    def five(pid):
+        monkeypatch.setenv("MIMIC_SPREAD_OWN", "1")
+        vm.SetSpread(-1)
+        batch(pid, 14, "spread_own")
+        monkeypatch.setenv("MIMIC_SPREAD_OWN", "0")
+        vm.SetSpread(1)
+        batch(pid, 64, "spread")
+        vm.SetSpread(0)
+        lens, r0 = batch(pid, 14, "jit")
+        batch(pid, 14, "jit", ctx=live)
+        buf, off, ln = W.make_packets(1, sizes=(67,), seed=seed[0])
+        o = ovm.run_xdp_batch(opids[pid], buf.copy(), off, ln, np.array([3], np.int32))
+        e = _run(vm, pids[pid], bytes(buf[int(off[0]):int(off[0]) + int(ln[0])]), ingress=0, cpu=3)
+        assert e["exec"] == "jit" and e["err"] is None
+        assert (e["regs"][0], e["steps"], e["status"]) == (int(o["r0"][0]), int(o["steps"][0]), int(o["status"][0]))
+        assert [maps["c"].Values(c) for c in range(V)] == [ovm.map_values(omids["c"], c) for c in range(V)], (pid, "proc")
+        return lens, r0
+
+    lens, r0 = five(0)
+    assert (r0 == 2).all()
+    name, raw, rel = two.progs[1]
+    pids.append(vm.AddProgram(M.ProgramSpec(name, raw, list(rel))))
+    opids.append(ovm.prog_load(name, raw, [(s, omids[n]) for s, n in rel]))
+    lens, r0 = five(1)
+    assert np.array_equal(r0, lens.astype(np.int64))   # the new program's verdict on every packet
+    live.close()
+    ovm.close()
     vm.close()
