@@ -14,9 +14,13 @@
 #include "skb.h"
 #include "../../include/mimic_amd.h"
 
-typedef uint16_t __attribute__((aligned(1))) u16u;
-typedef uint32_t __attribute__((aligned(1))) u32u;
-typedef uint64_t __attribute__((aligned(1))) u64u;
+// ld_n / st_n access the same bytes in different sizes (a 2-byte store into a word that an 8-byte load
+// reads back): may_alias, or type-based alias analysis lets the compiler keep the word an earlier load
+// of the same address fetched across the store (found by tests/test_gpu_memmatrix.py's sk_buff forms:
+// ldx8 [data+56]; stx2 [data+63]; ldx8 [data+56] returned the first load's value)
+typedef uint16_t __attribute__((aligned(1), may_alias)) u16u;
+typedef uint32_t __attribute__((aligned(1), may_alias)) u32u;
+typedef uint64_t __attribute__((aligned(1), may_alias)) u64u;
 
 #define DEV static __device__ __forceinline__
 // pop-only launches insert without stripe locks (hashmap.h h_insert_nolock); MIMIC_JIT_DEFS=

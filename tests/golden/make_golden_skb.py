@@ -395,6 +395,15 @@ case("leak_data", "data of later processes", ld_field(S["data"]), [PKT4, PKT4, P
 case("stack_same", "the stack entry is reused", [A.mov64_reg(0, 10), A.exit_()], [PKT4, PKT6],
      [e(St + 256, steps=2), e(St + 256, steps=2)])
 
+# ---- a store into a word that was loaded before and is loaded again (found by tests/memmatrix.py) ----
+# data + 63 computed from a packet byte (the TTL, 64), so the compiler cannot place the store: the JIT
+# kept the first load's word across the 2-byte store (ld_n / st_n without may_alias, runtime.h) and
+# returned 0x...8889.  PKT4's bytes 56..63 are 82 .. 89; the store puts 0x88 at 63 and 0x89 at 64.
+case("store_into_reloaded_word", "SKBuff packet Store then Load, BigEndian (emulator_linux_sk_buff.go:108-121)",
+     [A.ldx(4, 2, 1, S["data"]), A.ldx(8, 8, 2, 56), A.ldx(1, 7, 2, 22), A.alu64("add", 7, -1), A.mov64_reg(9, 2),
+      A.alu64("add", 9, 7, reg=True), A.stx(2, 9, 0, 8), A.ldx(8, 0, 2, 56), A.exit_()], [pad(PKT4, 100)],
+     [e(0x8283848586878888, steps=9)])
+
 if __name__ == "__main__":
     with open(os.path.join(HERE, "kat_skb.json"), "w") as f:
         json.dump({"generator": "tests/golden/make_golden_skb.py", "cases": CASES}, f, indent=1)
