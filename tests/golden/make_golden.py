@@ -524,6 +524,38 @@ arsh_x("arsh32_x_64_negative", False, 0xFFFF_FFFF_8000_0000, 64, M64, "inst.go:1
 arsh_x("arsh32_x_64_positive", False, 0xFFFF_FFFF_7FFF_FFFF, 64, 0, "inst.go:121-125 (int32(dst): the high word is dropped)")
 
 
+# ------------------------------------------------------------------------------------------
+# helper arguments at the edges tests/helpmatrix.py walks per lane, as literal vectors (a group of their own)
+# ------------------------------------------------------------------------------------------
+JIT_GROUP = 2
+STACK_END = 2048 - 256          # r10 + STACK_END is the byte past the stack's backing (vm.go:208-210)
+key_at = lambda o: [A.mov64_reg(2, 10), A.alu64("add", 2, o), A.ld_map_fd(1, "arr"), A.call(1)]  # noqa: E731
+straight("lookup_key_last_bytes_of_stack", [A.st(4, 10, STACK_END - 4, 1)] + key_at(STACK_END - 4) + [A.ldx(4, 0, 0, 0)], 2,
+         "emulator_linux_helpers.go:463-468, memory_plain.go:27-34 (off + 4 == len)", maps=[ARR], map_init=[("arr", k(1), k(2), 0)])
+case("lookup_key_one_past_last_bytes_of_stack", key_at(STACK_END - 3) + [A.exit_()], e(status=KEY, steps=5, err_pc=4),
+     "emulator_linux_helpers.go:463-468, memory_plain.go:27-34 (off + 4 > len)", maps=[ARR])
+case("tailcall_index_is_uint32_of_r3", [A.mov64_imm(0, 1), A.ld_map_fd(2, "progs"), A.ld_imm64(3, (1 << 32) + 1), A.call(12),
+                                        A.alu64("add", 0, 1000), A.exit_()], e(r0=6, steps=8),
+     "emulator_linux_helpers.go:683-685 (uint32(R3))", maps=[PA], extra_progs=[("t", tc_target)], prog_array=[("progs", 1, 1)])
+map_at = lambda o: [A.st(4, 10, -4, 1), A.mov64_reg(2, 10), A.alu64("add", 2, -4), A.ld_map_fd(1, "arr"), A.alu64("add", 1, o),  # noqa: E731
+                    A.call(1)]
+straight("lookup_map_object_inclusive_end", map_at(8) + [A.ldx(4, 0, 0, 0)], 2,
+         "memory_controller.go:117-145 (Addr + Size is the entry's), emulator_linux_helpers.go:417-422", maps=[ARR],
+         map_init=[("arr", k(1), k(2), 0)])
+case("lookup_map_object_one_past_end", map_at(9) + [A.exit_()], e(status=MAP_PTR, steps=7, err_pc=6),
+     "emulator_linux_helpers.go:426-436 (the values' first word, 0, as a double pointer)", maps=[ARR], map_init=[("arr", k(1), k(2), 0)])
+# bytes 0 .. 15 of the values are 01 .. 10; entry 1 (bytes 12 .. 23) is updated from bytes 8 .. 19: the reference copies
+# the value out first (emulator_linux_helpers.go:537-543), so bytes 16 .. 23 end as 0d 0e 0f 10 00 00 00 00; a forward
+# copy in 8-byte words would read bytes 16 .. 19 after it wrote them (0x100f0e0d100f0e0d)
+OV = dict(name="ov", type=2, key_size=4, value_size=12, max_entries=3)
+straight("update_value_overlaps_destination",
+         [A.st(4, 10, -4, 0), A.mov64_reg(2, 10), A.alu64("add", 2, -4), A.ld_map_fd(1, "ov"), A.call(1), A.mov64_reg(6, 0),
+          A.ld_imm64(3, 0x0807060504030201), A.stx(8, 6, 0, 3), A.ld_imm64(3, 0x100F0E0D0C0B0A09), A.stx(8, 6, 8, 3),
+          A.st(4, 10, -4, 1), A.mov64_reg(2, 10), A.alu64("add", 2, -4), A.mov64_reg(3, 6), A.alu64("add", 3, 8),
+          A.ld_map_fd(1, "ov"), A.mov64_imm(4, 0), A.call(2), A.ldx(8, 0, 6, 16)], 0x100F0E0D,
+         "emulator_linux_helpers.go:537-543, emulator_linux_map_array.go:112 (memmove)", maps=[OV])
+
+
 def main():
     out = os.path.join(HERE, "kat.json")
     with open(out, "w") as f:
