@@ -76,7 +76,8 @@ enum mimic_status {
     MIMIC_PANIC_HELPER_NEG = 21,     /* negative helper id, emulator_linux_.go:126 */
     MIMIC_ERR_STEP_LIMIT = 22,       /* step budget: the engine's watchdog next to Run's ctx (mimic_run_*_ctx) */
     MIMIC_ERR_CALL_DEPTH = 23,       /* > MIMIC_MAX_FRAMES nested BPF-to-BPF calls */
-    MIMIC_ERR_ENGINE_HELPER = 24,    /* helper the reference emulates but this engine does not */
+    MIMIC_ERR_ENGINE_HELPER = 24,    /* helper the reference emulates but this engine does not: 5, 7, 25, 38, 87-89
+                                        (helpers 1, 2, 3, 8, 9 = bpf_skb_store_bytes, 12 and 65 run on the device) */
     MIMIC_ERR_NO_CPU = 25,
     MIMIC_ERR_CTX_ACCESS = 26,       /* __sk_buff / bpf_sock / bpf_flow_keys field error, emulator_linux_sk_buff.go */
     MIMIC_PANIC_SLICE = 27,          /* Go slice-bounds panic in those accessors */

@@ -45,6 +45,7 @@ FN_MAP_LOOKUP_ELEM = 1
 FN_MAP_UPDATE_ELEM = 2
 FN_MAP_DELETE_ELEM = 3
 FN_GET_SMP_PROCESSOR_ID = 8
+FN_SKB_STORE_BYTES = 9
 FN_TAIL_CALL = 12
 FN_XDP_ADJUST_TAIL = 65
 

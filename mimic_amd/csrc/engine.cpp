@@ -34,7 +34,7 @@
 #include "jit.h"
 #include "skb.h"
 
-extern "C" int mimic_launch_xdp(const KParams *kp, const KParams *d_kp, hipStream_t st);
+extern "C" int mimic_launch_xdp(const KParams *kp, const KParams *d_kp, int store_bytes, hipStream_t st);
 extern "C" int mimic_launch_xdp_resume(const KParams *kp, hipStream_t st);
 
 extern "C" int mimic_launch_hash_rebuild(uint8_t *arena, const DMap *m, uint32_t force, hipStream_t st);
@@ -175,6 +175,7 @@ struct mimic_vm {
     bool tables_dirty = true;
     bool prog_deletes = false;   // some loaded program calls map_delete_elem (helper 3)
     bool prog_updates = false;   // some loaded program calls map_update_elem (helper 2)
+    bool prog_store_bytes = false;   // some loaded program calls bpf_skb_store_bytes (helper 9): interp.hip SKBST
     uint8_t *priv = nullptr;
     uint64_t priv_bytes = 0;
     uint32_t priv_lanes = 0;
@@ -483,7 +484,7 @@ static uint32_t predecode(const DInsn &x, int64_t i, int64_t n) {
             if (hc == 0) return err(MIMIC_ERR_HELPER_UNIMPLEMENTED);
             if (hc == 2) return err(MIMIC_ERR_HELPER_CANT_EMULATE);
             switch (imm32) {
-            case 1: case 2: case 3: case 8: case 12: case 65: return a | H_CALL;
+            case 1: case 2: case 3: case 8: case 9: case 12: case 65: return a | H_CALL;
             default: return err(MIMIC_ERR_ENGINE_HELPER);
             }
         }
@@ -569,9 +570,11 @@ static int upload_tables(mimic_vm *vm) {
     build_host_tables(vm->progs, vm->h_all, vm->h_dp);
     vm->prog_deletes = false;
     vm->prog_updates = false;
+    vm->prog_store_bytes = false;
     for (auto &x : vm->h_all) {
         if (AUX_H(x.aux) == H_CALL && (uint32_t)x.k == 3) vm->prog_deletes = true;
         if (AUX_H(x.aux) == H_CALL && (uint32_t)x.k == 2) vm->prog_updates = true;
+        if (AUX_H(x.aux) == H_CALL && (uint32_t)x.k == 9) vm->prog_store_bytes = true;
     }
     // map hints of LD_IMM64 constants that are map objects (AUX_MAPHINT): the JIT's inline
     // helpers check the map at run time, so a hint only selects a fast path
@@ -2461,13 +2464,13 @@ static int run_xdp_impl(mimic_vm *vm, uint32_t prog_id, const mimic_xdp_batch *b
         if (ji.defer && mimic_launch_xdp_resume(&kp, st))
             return fail(vm, MIMIC_EDEVICE, "launch: %s", hipGetErrorString(hipGetLastError()));
     } else if (step) {   // the stepping kernel takes its parameters by value: no slot, no copy
-        if (mimic_launch_xdp(&kp, nullptr, st))
+        if (mimic_launch_xdp(&kp, nullptr, 0, st))
             return fail(vm, MIMIC_EDEVICE, "launch: %s", hipGetErrorString(hipGetLastError()));
     } else {  // the batch interpreter reads its launch parameters from a device copy
         const KParams *dkp = nullptr;
         const int slot = kp_slot(vm, kp, st, &dkp);
         if (slot < 0) return slot;
-        if (mimic_launch_xdp(&kp, dkp, st))
+        if (mimic_launch_xdp(&kp, dkp, vm->prog_store_bytes ? 1 : 0, st))
             return fail(vm, MIMIC_EDEVICE, "launch: %s", hipGetErrorString(hipGetLastError()));
         HIP_OK(vm, hipEventRecord(vm->kp_ev[slot], st));   // the slot is free again once this passes
         vm->kp_used[slot] = true;

@@ -5,7 +5,7 @@
 //   VM.NewProcess (vm.go:198-235) + LinuxContextXDP.Load (context_xdp_md.go:47-115)
 //   Process.SetCPUID (vm.go:268-283)
 //   Process.Run -> Process.Step -> instructions[op] (vm.go:291-360, inst.go, inst_gen.go)
-//   LinuxEmulator.CallHelperFunction (emulator_linux_.go:125-194) for helpers 1/2/3/8/12/65
+//   LinuxEmulator.CallHelperFunction (emulator_linux_.go:125-194) for helpers 1/2/3/8/9/12/65
 //   Process.Cleanup (vm.go:363-374)
 // with the reference's effective semantics, bit for bit.
 //
@@ -82,8 +82,13 @@ static __device__ __noinline__ void step_warm(const KParams &kp, uint32_t t, uin
 // (a process a JIT lane deferred, then the lane's remaining packets) in or out, so the batch
 // kernel carries none of their registers (146 -> the batch kernel's own budget, 3 -> 4 waves per
 // SIMD).
+//
+// SKBST compiles bpf_skb_store_bytes (helper 9: its byte mover between two resolved regions) in.  The
+// batch kernel cannot hold it inside its 4-wave budget (64 spilled VGPRs / 112 B of scratch with it,
+// 16 / 64 B without), so it lives in an instance of its own, mimic_xdp_store_kernel, which the engine
+// launches when some loaded program calls helper 9; the step and resume kernels always carry it.
 enum { MODE_BATCH = 0, MODE_STEP = 1, MODE_RESUME = 2 };
-template <int MODE>
+template <int MODE, bool SKBST>
 static __device__ __forceinline__ void xdp_body(const KParams *__restrict__ kpp, uint32_t goff = 0) {
     const KParams &kp = *kpp;  // device copy (engine.cpp kp_slot) or the kernarg segment: fields load where used
     StepState *const STP = MODE == MODE_STEP ? kp.step : nullptr;
@@ -397,11 +402,14 @@ static __device__ __forceinline__ void xdp_body(const KParams *__restrict__ kpp,
                         else if (hn == 2) ho = helper_update(kp, L, REG(1), REG(2), REG(3));
                         else if (hn == 3) ho = helper_delete(kp, L, REG(1), REG(2));
                         else if (hn == 8) { ho.r0 = (uint64_t)(int64_t)L.cpu; ho.set_r0 = true; }
+                        // emulator_linux_helpers.go:608-647 (mimic_launch_xdp picks the instance from the
+                        // loaded programs; a call 9 in an instance without it ends below as an engine error)
+                        else if (SKBST && hn == 9) ho = helper_skb_store_bytes(kp, L, REG(1), REG(2), REG(3), REG(4));
                         else if (hn == 12) ho = helper_tailcall(kp, L, REG(2), REG(3));
                         else {  // 65: bpf_xdp_adjust_tail, emulator_linux_helpers.go:842-864
                             const Ref R = resolve(kp, L, (uint32_t)REG(1));
                             const bool plain20 = (R.rk == RK_GLOBAL || R.rk == RK_STACK) && R.map < 0 && R.limit == 20;
-                            if (plain20) ho.st = MIMIC_ERR_ENGINE_HELPER;
+                            if (plain20 || hn != 65) ho.st = MIMIC_ERR_ENGINE_HELPER;   // (any other number: engine assertion)
                             else { ho.r0 = (uint64_t)(int64_t)-22; ho.set_r0 = true; }
                         }
                         st = ho.st;
@@ -503,13 +511,15 @@ static __device__ __forceinline__ void xdp_body(const KParams *__restrict__ kpp,
 #undef REG
 }
 
-extern "C" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void mimic_xdp_kernel(const KParams *__restrict__ kpp) { xdp_body<MODE_BATCH>(kpp); }
+extern "C" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void mimic_xdp_kernel(const KParams *__restrict__ kpp) { xdp_body<MODE_BATCH, false>(kpp); }
+// the batch kernel of a VM whose programs call bpf_skb_store_bytes (3 waves per SIMD, nothing spilled)
+extern "C" __global__ __launch_bounds__(256) void mimic_xdp_store_kernel(const KParams *__restrict__ kpp) { xdp_body<MODE_BATCH, true>(kpp); }
 // Process.Step / Run: launch parameters by value (no parameter slot, no copy ahead of the launch)
 extern "C" __global__ __launch_bounds__(256) void mimic_xdp_step_kernel(const KParams kp_arg) {
     (void)kp_arg;
     const KParams __attribute__((address_space(4))) *k4 =
         (const KParams __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr();
-    xdp_body<MODE_STEP>((const KParams *)k4);
+    xdp_body<MODE_STEP, true>((const KParams *)k4);
 }
 // after a JIT kernel with deferred slow paths, with the same launch parameters (by value: read
 // in place from the kernarg segment, as the JIT kernels do)
@@ -522,7 +532,7 @@ extern "C" __global__ __launch_bounds__(256) void mimic_xdp_resume_kernel(const 
         (const KParams __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr();
     const KParams *kp = (const KParams *)k4;
     const uint32_t lanes = kp->lanes, stride = gridDim.x * blockDim.x;
-    for (uint32_t off = 0; off < lanes; off += stride) xdp_body<MODE_RESUME>(kp, off);
+    for (uint32_t off = 0; off < lanes; off += stride) xdp_body<MODE_RESUME, true>(kp, off);
 }
 
 // Sum of a per-CPU u64 array over cpus: out[k] = sum_c base[c*stride + 8k] (the "sum over CPUs"
@@ -869,10 +879,12 @@ extern "C" int mimic_launch_xdp_resume(const KParams *kp, hipStream_t st) {
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-extern "C" int mimic_launch_xdp(const KParams *kp, const KParams *d_kp, hipStream_t st) {
+// store_bytes: some loaded program calls helper 9 (the batch kernel's instance with its mover)
+extern "C" int mimic_launch_xdp(const KParams *kp, const KParams *d_kp, int store_bytes, hipStream_t st) {
     const uint32_t blocks = (kp->lanes + 255) / 256;
     if (blocks == 0) return 0;
     if (kp->step) hipLaunchKernelGGL(mimic_xdp_step_kernel, dim3(blocks), dim3(256), (size_t)kp->step_ins_n * sizeof(DInsn), st, *kp);
+    else if (store_bytes) hipLaunchKernelGGL(mimic_xdp_store_kernel, dim3(blocks), dim3(256), 0, st, d_kp);
     else hipLaunchKernelGGL(mimic_xdp_kernel, dim3(blocks), dim3(256), 0, st, d_kp);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -100,6 +100,7 @@ class Gen {
         hchunk_knob = num("MIMIC_JIT_HCHUNK", 32);
         skb_fields = off("MIMIC_JIT_SKBFIELD");
         skb_lds_knob = off("MIMIC_JIT_SKBLDS");
+        skb_store = off("MIMIC_JIT_SKBSTORE");
         sm_lds_knob = off("MIMIC_JIT_SMLDS");
         inc_knob = off("MIMIC_JIT_INC");
         hash_fast = off("MIMIC_JIT_HASH");
@@ -143,6 +144,7 @@ class Gen {
     int cold_mode = 0;         // MIMIC_JIT_COLD: 0 auto, 1 call, 2 inline, 3 defer
     bool skb_fields = true;    // MIMIC_JIT_SKBFIELD=0: no per-field sk_buff access code
     bool skb_lds_knob = true;  // MIMIC_JIT_SKBLDS=0: no LDS copy of the sk_buff record
+    bool skb_store = true;     // MIMIC_JIT_SKBSTORE=0: no inline bpf_skb_store_bytes (store_bytes_fast)
     bool inc_knob = true;      // MIMIC_JIT_INC=0: no fused counter increments (fusable_inc)
     bool sm_lds_knob = true;   // MIMIC_JIT_SMLDS=0: stack validity masks in VGPRs in defer mode too
     bool hash_fast = true;     // MIMIC_JIT_HASH=0: no inline hash-map lookups
@@ -1667,6 +1669,8 @@ class Gen {
             for (int k = 0; k < 8; k++)
                 if (!call.compare(0, strlen(kinds[k]), kinds[k]))
                     return "COLD_CALL_K(" + std::to_string(4 * k) + ", " + call + ", " + std::to_string(i) + ");";
+            // the eight nibbles are taken: bpf_skb_store_bytes counts as a store
+            if (!call.compare(0, 17, "cold_store_bytes(")) return "COLD_CALL_K(4, " + call + ", " + std::to_string(i) + ");";
         }
         return "COLD_CALL(" + call + ", " + std::to_string(i) + ");";
     }
@@ -1706,6 +1710,7 @@ class Gen {
                 switch ((uint32_t)x.k) {
                 case 1: case 3: use = bit(1) | bit(2); break;
                 case 2: use = bit(1) | bit(2) | bit(3); break;
+                case 9: use = bit(1) | bit(2) | bit(3) | bit(4); break;
                 case 12: use = bit(2) | bit(3); break;
                 case 65: use = bit(1); break;
                 default: break;
@@ -2142,6 +2147,20 @@ class Gen {
         return -1;
     }
 
+    // the `mov rR, imm` slot (64- or 32-bit) whose constant register r still holds at slot i (same basic
+    // block, r not written in between; a call is taken as clobbering it, as reg_def does), or -1
+    int64_t mov_imm_def(const ProgView &p, uint32_t i, uint32_t r) const {
+        for (int64_t j = (int64_t)i - 1; j >= (int64_t)blk_start; j--) {
+            const DInsn &x = p.ins[j];
+            const uint32_t h = AUX_H(x.aux), d = insn_dst(x);
+            if ((h == H_ALU64 || h == H_ALU32) && d == r && (insn_op(x) & 0xf0) == 0xb0 && !(x.aux & AUX_X)) return j;
+            if ((h == H_ALU64 || h == H_ALU32 || h == H_LDX || h == H_SLOW || h == H_LDIMM) && d == r) return -1;
+            if (h == H_LDABS || h == H_CALL_LOCAL || h == H_CALL) return -1;
+        }
+        return -1;
+    }
+    static constexpr uint64_t kStoreFastMax = 32;   // runtime.h SKB_STORE_FAST_MAX
+
     void helper(const ProgView &p, uint32_t i) {  // emulator_linux_.go:125-194
         const DInsn &x = p.ins[i];
         const uint32_t h = (uint32_t)x.k;
@@ -2190,6 +2209,15 @@ class Gen {
         case 8:
             E.line("    r0 = (uint64_t)(int64_t)L.cpu;");
             break;
+        case 9: {  // bpf_skb_store_bytes: inline when R4 is a small mov immediate of this block (store_bytes_fast)
+            const int64_t j = fast_paths && skb_store && ctx == CTX_SKB ? mov_imm_def(p, i, 4) : -1;
+            const uint64_t n = j < 0 ? 0 : AUX_H(p.ins[j].aux) == H_ALU64 ? p.ins[j].k : (uint64_t)(uint32_t)p.ins[j].k;
+            if (n >= 1 && n <= kStoreFastMax)
+                E.line("    if (!store_bytes_fast<%uu>(kp, L, SK_, r1, r2, r3, r4, r0)) %s", (uint32_t)n, cold("cold_store_bytes(kp, sp_)", i).c_str());
+            else
+                E.line("    %s", cold("cold_store_bytes(kp, sp_)", i).c_str());
+            break;
+        }
         case 12: {
             // inline when R2 is a prog-array object named by an LD_IMM64 in this block
             const int64_t j = fast_paths && tail_inline ? reg_def(p, i, 2) : -1;

@@ -134,7 +134,7 @@ enum Handler : uint32_t {
     H_ST = 9,
     H_STX = 10,
     H_EXIT = 11,
-    H_CALL = 12,       // helper 1/2/3/8/12/65
+    H_CALL = 12,       // helper 1/2/3/8/9/12/65
     H_CALL_LOCAL = 13, // BPF-to-BPF
     H_LDABS = 14,      // LD_ABS / LD_IND (AUX_X = IND); R6 must be the sk_buff (emulator_linux_.go:198-288)
 };

@@ -773,6 +773,32 @@ DEV void copy_into(const KParams &kp, const Lane &L, const Ref &src, uint8_t *ds
     }
 }
 
+// memmove of n bytes from a readable VM region into the lane's packet memory (bpf_skb_store_bytes:
+// vmmem.Read into a fresh slice, then PlainMemory.Write, memory_plain.go:106-118).  The caller has
+// checked both ends, so every access stays inside the region and inside [dst, dst + n).  Chunks of
+// at most 8 bytes, each read completely before it is written; the first one ends at a word boundary
+// of the source, so a stack source is read a whole word at a time (stack_load: the LDS window,
+// private memory and the validity bits, unwritten bytes as zero) whatever its alignment.  A source
+// in the same packet that the destination overlaps from above is copied from its end.
+DEV void copy_to_packet(const KParams &kp, const Lane &L, const Ref &src, uint8_t *dst, uint32_t n) {
+    if (src.rk == RK_BEPKT || src.rk == RK_GLOBAL) {
+        const uint8_t *s = src.ptr + src.off;
+        if (s < dst && dst < s + n) {
+            for (uint32_t e = n; e > 0;) {
+                const uint32_t c = e < 8 ? e : 8;
+                e -= c;
+                st_n(dst + e, c, ld_n(s + e, c));
+            }
+            return;
+        }
+    }
+    uint32_t c = 8 - (src.off & 7);
+    for (uint32_t o = 0; o < n; o += c, c = 8) {
+        if (c > n - o) c = n - o;
+        st_n(dst + o, c, region_load(kp, L, src, src.off + o, c));
+    }
+}
+
 // hash-map key words: derefMapKey (emulator_linux_helpers.go:449-471) copies the key out of VM
 // memory once, into the lane's key scratch in private memory (qword-interleaved like the stack)
 struct KeyPriv {
@@ -976,6 +1002,31 @@ DEV HelperOut helper_tailcall(const KParams &kp, const Lane &L, uint64_t r2, uin
     }
     o.tail = true;
     o.new_prog = (uint32_t)P.prog;
+    return o;
+}
+
+// bpf_skb_store_bytes (emulator_linux_helpers.go:608-647): R1 = ctx, R2 = offset in the packet memory
+// (from the start of the headroom: 32 is the frame's first byte), R3 = source, R4 = length; R5 (the
+// flags) is never read.  In the reference's order: R1 must resolve to the process's *SKBuff (an
+// xdp_md VM has none); R3 to a VMMem; make([]byte, R4) panics above Go's maxAlloc (2^48); the source
+// is read completely (VMMem.Read: readable()), then written with PlainMemory.Write, which fails as a
+// whole past the tailroom's end.  A length in (2^32, 2^48] would make the reference allocate that
+// much before its Read fails: answered here as that Read's failure, without the allocation.
+// The snapshot and IP slices of the SkbRec keep the bytes the packet had at Load (gopacket copied them).
+DEV HelperOut helper_skb_store_bytes(const KParams &kp, const Lane &L, uint64_t r1, uint64_t r2, uint64_t r3, uint64_t r4) {
+    HelperOut o = {0, 0, false, false, 0, 0, 0, nullptr};
+    if (resolve(kp, L, (uint32_t)r1).rk != RK_SKB) { o.st = MIMIC_ERR_CTX_ACCESS; return o; }
+    const Ref V = resolve(kp, L, (uint32_t)r3);
+    if (!is_vmmem(V.rk)) { o.st = MIMIC_ERR_HELPER_VALUE; return o; }
+    if (r4 > (1ull << 48)) { o.st = MIMIC_PANIC_SLICE; return o; }
+    if (r4 > 0xffffffffull || !readable(V, (uint32_t)r4)) { o.st = MIMIC_ERR_HELPER_VALUE; return o; }
+    const uint32_t at = (uint32_t)r2, n = (uint32_t)r4;
+    if ((uint64_t)at + n > L.M) { o.st = MIMIC_ERR_MEM_BOUNDS; return o; }
+    copy_to_packet(kp, L, V, L.pkt + at, n);
+    // a write not wholly inside the frame: the next launch's prep reads the rooms again
+    if (n && (at < SKB_HEADROOM || at + n > L.M - SKB_TAILROOM)) skb_room_mark(kp);
+    o.r0 = 0;
+    o.set_r0 = true;
     return o;
 }
 
@@ -1214,6 +1265,10 @@ COLD void cold_tailcall(const KParams &kp, Spill &S) {
     S.tail = !ho.st && ho.tail;
     S.new_prog = ho.new_prog;
 }
+COLD void cold_store_bytes(const KParams &kp, Spill &S) {
+    COLD_OPAQUE();
+    cold_take(S, helper_skb_store_bytes(kp, S.L, S.r[1], S.r[2], S.r[3], S.r[4]));
+}
 // LD_ABS / LD_IND through the generic path (emulator_linux_.go:198-288): R0, then R1-R5 = 0
 COLD void cold_ldabs(const KParams &kp, Spill &S, uint32_t x, uint32_t n, bool bad_src) {
     COLD_OPAQUE();
@@ -1328,6 +1383,39 @@ DEV int tail_fast(const KParams &kp, const Lane &L, uint32_t mid, uint64_t r2, u
         return -1;
     }
     return (int)cget(kp.segs, (uint32_t)si).id;
+}
+
+// Inline form of helper 9 (bpf_skb_store_bytes) for a length N the JIT read off the mov immediate that
+// set R4 (1 <= N <= SKB_STORE_FAST_MAX; compared with R4 here, like every other guess, so a wrong one
+// only costs the slow path).  It applies when R1 lies in this process's sk_buff entry `sk`, the N
+// source bytes lie in the stack entry and the destination lies wholly in the frame (no room byte is
+// written, so the rooms-clean word stays, as with the JIT's frame-only packet store).  Then
+// helper_skb_store_bytes reduces to the lines below: the source's aligned stack words (stack_load: LDS
+// window or private memory, unwritten words as zero) are shifted into place and stored in chunks of 8
+// bytes, all read before the first is written.  Returns false when the case does not apply
+// (cold_store_bytes).
+#define SKB_STORE_FAST_MAX 32u
+template <uint32_t N>
+DEV bool store_bytes_fast(const KParams &kp, const Lane &L, uint32_t sk, uint64_t r1, uint64_t r2, uint64_t r3, uint64_t r4,
+                          uint64_t &r0) {
+    static_assert(N >= 1 && N <= SKB_STORE_FAST_MAX, "the inline form's cap");
+    if (r4 != N || !L.rec || (uint32_t)r1 - sk > SKB_STRUCT_SIZE) return false;
+    const uint32_t so = (uint32_t)r3 - kp.static_next, at = (uint32_t)r2;
+    if ((uint64_t)so + N > kp.stack_size) return false;
+    if (at < SKB_HEADROOM || (uint64_t)at + N > L.M - SKB_TAILROOM) return false;
+    constexpr uint32_t NW = (N + 14) / 8;   // aligned words a run of N bytes can touch
+    const uint32_t base = so & ~7u, sh = 8 * (so & 7);
+    uint64_t w[NW + 1];
+#pragma unroll
+    for (uint32_t k = 0; k < NW; k++) w[k] = base + 8 * k < so + N ? stack_load(kp, L, base + 8 * k, 8) : 0;
+    w[NW] = 0;
+#pragma unroll
+    for (uint32_t k = 0; 8 * k < N; k++) {
+        const uint64_t v = sh ? (w[k] >> sh) | (w[k + 1] << (64 - sh)) : w[k];
+        st_n(L.pkt + at + 8 * k, N - 8 * k < 8 ? N - 8 * k : 8, v);
+    }
+    r0 = 0;
+    return true;
 }
 
 // ---------------------------------------------------------------------------------------

@@ -878,6 +878,78 @@ def skb_programs(progs: str = "progs", flows: str = "flows", stats: str = "stats
     return out, maps, prog_array
 
 
+# ---------------------------------------------------------------------------------------------
+# tc rewrite: swap the MAC addresses of an IPv4 frame and decrement its TTL.  Two programs with the
+# same effect on the packet: one writes through bpf_skb_store_bytes (helper 9), one with byte stores
+# through ctx->data.
+# ---------------------------------------------------------------------------------------------
+def _skb_rewrite_head():
+    """r6 = ctx, r7 = data; frames shorter than an IPv4 header or of another ethertype go to `out`.
+    The new bytes are built on the stack: [R10 - 16, R10 - 4) the MACs swapped, R10 - 20 / - 19 the
+    patched checksum (ip_decrease_ttl: + 0x0100 with the carry folded back), R10 - 18 the new TTL
+    (in r8).  Packet memory is big endian (emulator_linux_sk_buff.go:108-121): a 2-byte load of the
+    checksum gives the number the patch is made on."""
+    S = A.SKB
+    it = [A.mov64_reg(6, 1), A.ldx(4, 2, 6, S["len"]), A.jmp("jlt", 2, 34, "out"),
+          A.ld_abs(2, 12), A.jmp("jne", 0, ETH_P_IP, "out"), A.ldx(4, 7, 6, S["data"])]
+    for k in range(12):
+        it += [A.ldx(1, 2, 7, k), A.stx(1, 10, -16 + (k + 6) % 12, 2)]
+    it += [A.ldx(1, 8, 7, 22), A.alu64("add", 8, 255), A.alu64("and", 8, 0xFF),
+           A.ldx(2, 9, 7, 24), A.alu64("add", 9, 0x100), A.mov64_reg(2, 9), A.alu64("rsh", 2, 16), A.alu64("and", 9, 0xFFFF),
+           A.alu64("add", 9, 2, reg=True), A.mov64_reg(2, 9), A.alu64("rsh", 2, 8), A.stx(1, 10, -20, 2), A.stx(1, 10, -19, 9),
+           A.stx(1, 10, -18, 8)]
+    return it
+
+
+_SKB_REWRITE_TAIL = [A.mov64_reg(0, 8), A.exit_(), "out", A.mov64_imm(0, 0), A.exit_()]
+
+
+def prog_skb_rewrite() -> Program:
+    """tc program: for IPv4 frames swap the MACs with two 6-byte bpf_skb_store_bytes calls, decrement
+    the TTL and patch the header checksum with one 2-byte and one 1-byte call, return the new TTL;
+    other frames return 0."""
+    it = _skb_rewrite_head()
+    for at, src, n in ((0, -16, 6), (6, -10, 6), (24, -20, 2), (22, -18, 1)):
+        it += [A.mov64_reg(1, 6), A.mov64_imm(2, SKB_HEADROOM + at), A.mov64_reg(3, 10), A.alu64("add", 3, src),
+               A.mov64_imm(4, n), A.mov64_imm(5, 0), A.call(A.FN_SKB_STORE_BYTES)]
+    raw, rel = A.assemble(it + _SKB_REWRITE_TAIL)
+    return Program("skb_rewrite", raw, rel, [])
+
+
+def prog_skb_rewrite_direct() -> Program:
+    """prog_skb_rewrite's effect with byte stores through ctx->data (no helper call)."""
+    it = _skb_rewrite_head()
+    for k in range(12):
+        it += [A.ldx(1, 2, 10, -16 + k), A.stx(1, 7, k, 2)]
+    for at, src in ((24, -20), (25, -19), (22, -18)):
+        it += [A.ldx(1, 2, 10, src), A.stx(1, 7, at, 2)]
+    raw, rel = A.assemble(it + _SKB_REWRITE_TAIL)
+    return Program("skb_rewrite_direct", raw, rel, [])
+
+
+def skb_rewrite_expected(buf, off, lens):
+    """What the two rewrite programs leave of a make_skb_packets batch, for the packets whose context
+    loaded (a failed Load leaves its packet memory as it was): (packet buffer, R0 per packet).  Load
+    zeroes the rooms (context_sk_buff.go:110-119)."""
+    out = np.array(buf, dtype=np.uint8, copy=True)
+    o = np.asarray(off).astype(np.int64) + SKB_HEADROOM
+    L = np.asarray(lens).astype(np.int64)
+    out[(o - SKB_HEADROOM)[:, None] + np.arange(SKB_HEADROOM)] = 0
+    out[(o + L)[:, None] + np.arange(SKB_TAILROOM)] = 0
+    at = o[L >= 34]
+    at = at[(out[at + 12] == 0x08) & (out[at + 13] == 0x00)]
+    mac = np.stack([out[at + k] for k in range(12)], axis=1)
+    for k in range(12):
+        out[at + (k + 6) % 12] = mac[:, k]
+    ttl = (out[at + 22].astype(np.int64) + 255) & 0xFF
+    hc = ((out[at + 24].astype(np.int64) << 8) | out[at + 25]) + 0x100
+    hc = (hc & 0xFFFF) + (hc >> 16)
+    out[at + 22], out[at + 24], out[at + 25] = ttl, hc >> 8, hc & 0xFF
+    r0 = np.zeros(len(L), np.uint64)
+    r0[np.searchsorted(o, at)] = ttl
+    return out, r0
+
+
 def skb_flow_keys(buf, off, lens, every: int = 3, limit: int = 4096):
     """Keys the cfg-5 programs build for some of the batch's IPv4 / IPv6 frames (plain Ethernet):
     the hash map is pre-populated with every `every`-th distinct key, up to `limit`, value =

@@ -12,7 +12,7 @@ code objects are not compared: their other sections change with a comment in the
 the mode for a change that may alter the generated text (a comment, an alias, indentation) or a
 runtime header, and must leave the code as it was.
 
-Source.  No compile: for every label of sources(), under each setting of KNOBS (one child process
+Source.  No compile: for every label of sources(), under each setting of KNOBS and SUITE_KNOBS (one child process
 per setting, its environment cleared of every other MIMIC_JIT_ variable), OUT.json records the
 sha256 and byte length of the source text; the file's own sha256 is printed.  The source text
 is the code-object cache key, so two libraries whose files are equal generate the same kernels,
@@ -39,6 +39,9 @@ from mimic_amd import _lib, jit as J, workloads as W  # noqa: E402
 KNOBS = ("", "FAST=0", "PREFETCH=0", "XPF=1", "LPF=1", "NTRES=0", "CENSUS=1", "CTXCHECK=1", "COLD=call", "COLD=inline",
          "COLD=defer", "DISPATCH=0", "RETDISPATCH=1", "VC=0", "LDSSTK=0", "SKBLDS=0", "SMLDS=0", "SPEC=0", "COMBINE=0",
          "HCHUNK=0", "WAVES=2", "DEFS=A,B=2", "INC=0", "FWD=0", "ELIDE=0", "WINDOW=0", "HASH=0", "TAIL=0", "SKBFIELD=0")
+# settings that change no bench kernel (tests/test_jit_cpu.py holds every KNOBS entry to changing one): the inline
+# bpf_skb_store_bytes changes the kernels of tests/test_gpu_storematrix.py, which sources() lists
+SUITE_KNOBS = ("SKBSTORE=0",)
 
 
 def knob_env(setting: str) -> dict:
@@ -103,7 +106,7 @@ def source_digests() -> dict:
 def source_mode(out_path: str) -> None:
     clean = {k: v for k, v in os.environ.items() if not k.startswith("MIMIC_JIT_")}
     doc = {}
-    for setting in KNOBS:   # a child each: MIMIC_JIT_CTXCHECK is read once per process
+    for setting in KNOBS + SUITE_KNOBS:   # a child each: MIMIC_JIT_CTXCHECK is read once per process
         out = subprocess.run([sys.executable, os.path.abspath(__file__), "--source-child"], env=dict(clean, **knob_env(setting)),
                              capture_output=True, text=True, check=True).stdout
         doc[setting or "default"] = json.loads(out.strip().splitlines()[-1])
